@@ -2,6 +2,12 @@
 """bench.py — device-resident AES-256-GCM seal+open throughput (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--settle-ms MS] [--config 1..4] [--mode device|host]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: build the batch, one round trip,
+settle, W warmup steps, K timed steps, the line. --full adds, as runs of their own around the same
+timed steps, the kernel-timing events and the roofline, the sustained rate and the CPU baseline
+(below). --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 One step = seal every packet of the batch, then open every packet of it (in place, on device),
 i.e. one pass of the hot path (inside.go seal + outside.go open) over one 64 Ki x 1300 B batch.
@@ -17,6 +23,7 @@ holds (an idle MI355X needs a few hundred ms of load; the line's `settle` report
 --settle-ms 0 measures from a cold start).
 
 Printed (rank 0, one JSON line): value = (payload sealed + payload opened, all ranks) / time.
+The rest is in the line under --full only.
 roofline: the seal kernel's algorithmic bytes (2p+32 per packet) / its mean launch time, from HIP
 events bound to that kernel's own dispatch inside the timed region (neb_time_next_kernel: start and
 stop of the dominant kernel, no marker packets); traffic = PMC-measured HBM bytes
@@ -320,7 +327,15 @@ def main():
                     help="device mode: after the timed K steps, the same step repeated for about this long "
                          "(a fixed step count from the timed rate, barrier + sync around it, max over ranks): "
                          "the rate a long load holds, reported as `sustained` beside `value` (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="device mode: beside the headline, everything else this benchmark measures: kernel-timing "
+                         "events in the timed steps and the `roofline` from them, the `sustained` rate "
+                         "(--sustain-ms) and the `cpu_baseline` (off: a plain run sets up, settles, warms up, "
+                         "times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="device mode: after the timed steps, write what the last of them computed (status, "
+                         "opened slots, tags and sealed slots) as DIR/<name>.npy, float32 (dump_outputs)")
     ap.add_argument("--inproc", action="store_true",
                     help="device mode, --gpus N engines in ONE process (Nebula is one process): each engine its "
                          "own batch of the config's shape on its GPU (round-robin over the visible devices), "
@@ -337,6 +352,8 @@ def main():
                          "tunnel's packets and state on one device), or a contiguous packet range (range)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # tests: launch + aggregation, no GPU
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "device" or args.inproc or args.stub):
+        ap.error("--dump-outputs writes the device mode's outputs (--mode device, one process per GPU)")
 
     from nebula_amd.shard import Control, dist_env
 
@@ -454,8 +471,9 @@ def main():
     # chunk kernel, the ChaCha kernel) carry a start and a stop event bound to their own dispatch
     # (neb_time_next_kernel -> hipExtLaunchKernel): the kernel's own duration, with no marker packet
     # in the stream. Without a HIP handle (torch's events as the fallback) the events bracket the
-    # calls as markers instead, and kernel_ms is then an upper bound.
-    timed = [i for i in range(args.steps) if i % EV_EVERY == 0]
+    # calls as markers instead, and kernel_ms is then an upper bound. --full only: a plain run's
+    # timed steps are the seal and the open alone.
+    timed = [i for i in range(args.steps) if i % EV_EVERY == 0] if args.full else []
     ev = {i: tuple(TimingEvent() for _ in range(4)) for i in timed}
     bound = all(x.torch_ev is None for e in ev.values() for x in e)
     arm = L.lib().neb_time_next_kernel
@@ -481,35 +499,14 @@ def main():
     barrier()
     te = time.perf_counter()
     dt = te - ts
-    seal_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev.values()]))
-    open_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev.values()]))
-    call_ms = whole_seal_ms(db, stream)
-    seal_kernel = ""
-    if bound:  # the kernel the seal's events were bound to: one more armed (untimed) seal
-        e0 = ev[timed[0]]
-        arm(e0[0].h, e0[1].h)
-        db.seal()
-        seal_kernel = L.lib().neb_time_last_kernel().decode()
-        db.open()
-        torch.cuda.synchronize()
     st = db.status_host()
     assert (st == 0).all(), "open failed inside the timed region"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, db, st, rank)
     dt = ctrl.max(dt)
     total_payload = ctrl.sum(2 * payload * args.steps)
-    sus = sustained(args, ctrl, lambda: (db.seal(), db.open()), total_payload / args.steps, dt / args.steps * 1e3)
-    assert (db.status_host() == 0).all(), "open failed in the sustained run"
-    multi = hbm_over_ranks(ctrl, world, alg_bytes, seal_ms, ndev)
-
-    if rank != 0:
-        return
     value = total_payload / dt / GIB
-    achieved = multi["per_gpu"]["achieved_mean"]  # GB/s, seal kernel (rank 0's alone at N = 1)
     alg_name = "AES-256-GCM" if b.alg == L.ALG_AESGCM else "ChaCha20-Poly1305"
-    # the kernel the dispatch-bound events were bound to, as the library names it
-    kern_tag = seal_kernel if bound else "event brackets around the whole seal call"
-    # (shards: "C5/8" by tunnel, "C5/8r" by packet range)
-    pmc = pmc_config(f"C{cfg + 1}" + (f"/{args.shard_of}{'r' if args.shard_by == 'range' else ''}"
-                                      if cfg == 4 and args.shard_of else ""))
     lens = b.desc["len"].astype(np.int64)
     out = {
         "metric": "GiB/s device-resident AES-256-GCM seal+open, 1300 B pkts, 64 Ki batch"
@@ -520,7 +517,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "settle": settled,  # untimed, before the warmup (settle())
-        "sustained": sus,  # after the timed steps: the rate over ~--sustain-ms of the same step (sustained())
         "ms_per_step": round(dt / args.steps * 1e3, 4),
         "higher_is_better": True,
         # C5 is one 1 Mi-packet batch split over the GPUs (BASELINE.json "sharded over 8xMI355X"):
@@ -534,24 +530,55 @@ def main():
                    {"mean": round(float(lens.mean()), 1), "sizes": sorted(set(lens.tolist()))},
                    "keys": b.nkeys, "cipher": alg_name,
                    "parallelism": f"{world} GPU(s), independent packet shards, no collective"},
-        "roofline": {
-            "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": pmc["hbm_bytes_per_launch"] if pmc else None,
-            "binding": {k: pmc[k] for k in ("lds_busy", "valu_busy", "mean_ns", "source") if k in pmc} if pmc else None,
-            "kernel": kern_tag,
-            # the seal's dominant kernel between start / stop events bound to its dispatch
-            "kernel_ms": round(seal_ms, 4), "open_kernel_ms": round(open_ms, 4),
-            # the whole seal call (mixed keys: with its binning passes) between marker events,
-            # after the timed loop: a bound on the call, comparable across kernels and rounds
-            "seal_call_ms": round(call_ms, 4),
-            "seal_call_achieved": round(alg_bytes / (call_ms * 1e-3) / 1e9, 2),
-            "kernel_timing": "dispatch-bound events" if bound else "marker events around the call",
-            "algorithmic_bytes_per_launch": int(alg_bytes),
-            # every rank's own seal kernel: per GPU (min / mean / max over ranks) and the whole job
-            # against N x the HBM peak; devices = distinct GPUs the ranks ran on
-            "per_gpu": multi["per_gpu"], "aggregate": multi["aggregate"],
-        },
+    }
+    if not args.full:  # the plain run ends here
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
+
+    seal_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev.values()]))
+    open_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev.values()]))
+    call_ms = whole_seal_ms(db, stream)
+    seal_kernel = ""
+    if bound:  # the kernel the seal's events were bound to: one more armed (untimed) seal
+        e0 = ev[timed[0]]
+        arm(e0[0].h, e0[1].h)
+        db.seal()
+        seal_kernel = L.lib().neb_time_last_kernel().decode()
+        db.open()
+        torch.cuda.synchronize()
+        assert (db.status_host() == 0).all(), "open failed after the timed region"
+    sus = sustained(args, ctrl, lambda: (db.seal(), db.open()), total_payload / args.steps, dt / args.steps * 1e3)
+    assert (db.status_host() == 0).all(), "open failed in the sustained run"
+    multi = hbm_over_ranks(ctrl, world, alg_bytes, seal_ms, ndev)
+
+    if rank != 0:
+        return
+    achieved = multi["per_gpu"]["achieved_mean"]  # GB/s, seal kernel (rank 0's alone at N = 1)
+    # the kernel the dispatch-bound events were bound to, as the library names it
+    kern_tag = seal_kernel if bound else "event brackets around the whole seal call"
+    # (shards: "C5/8" by tunnel, "C5/8r" by packet range)
+    pmc = pmc_config(f"C{cfg + 1}" + (f"/{args.shard_of}{'r' if args.shard_by == 'range' else ''}"
+                                      if cfg == 4 and args.shard_of else ""))
+    # after the timed steps: the rate over ~--sustain-ms of the same step (sustained())
+    out["sustained"] = sus
+    out["roofline"] = {
+        "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": pmc["hbm_bytes_per_launch"] if pmc else None,
+        "binding": {k: pmc[k] for k in ("lds_busy", "valu_busy", "mean_ns", "source") if k in pmc} if pmc else None,
+        "kernel": kern_tag,
+        # the seal's dominant kernel between start / stop events bound to its dispatch
+        "kernel_ms": round(seal_ms, 4), "open_kernel_ms": round(open_ms, 4),
+        # the whole seal call (mixed keys: with its binning passes) between marker events,
+        # after the timed loop: a bound on the call, comparable across kernels and rounds
+        "seal_call_ms": round(call_ms, 4),
+        "seal_call_achieved": round(alg_bytes / (call_ms * 1e-3) / 1e9, 2),
+        "kernel_timing": "dispatch-bound events" if bound else "marker events around the call",
+        "algorithmic_bytes_per_launch": int(alg_bytes),
+        # every rank's own seal kernel: per GPU (min / mean / max over ranks) and the whole job
+        # against N x the HBM peak; devices = distinct GPUs the ranks ran on
+        "per_gpu": multi["per_gpu"], "aggregate": multi["aggregate"],
     }
     if world == 1 and not args.no_cpu_baseline:
         try:
@@ -602,6 +629,56 @@ def whole_seal_ms(db, stream, reps: int = 4) -> float:
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(z))
     return float(np.mean(ts))
+
+
+DUMP_SLOTS = 2048      # whole slots sampled for opened_slots / sealed_slots
+DUMP_TAGS = 131072     # packets whose tag is kept (every packet of a 64 Ki batch)
+DUMP_SEED = 0x64756D70  # "dump"
+
+
+def dump_outputs(path: str, db, status: np.ndarray, rank: int) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy
+    files under `path` (rank r > 0 appends `_rank<r>` to the names), so two builds run with the
+    same arguments can be compared output for output (the batch is a function of the seed alone):
+
+      status        (n,)            every packet's status word after the last step's open
+      opened_slots  (k, stride)     the arena after the last step (header | plaintext | tag space)
+      sealed_tags   (m, 16)         the tag of the sealed packet: it authenticates the AAD and all
+                                    the ciphertext, so it covers the whole of what the seal wrote
+      sealed_slots  (k, stride)     the sealed arena (header | ciphertext | tag)
+
+    The step seals and opens in place, so the sealed arena of the last step is gone once its open
+    has run; the open restores the plaintext and the seal depends on nothing else, so one more
+    seal here, untimed and after the clock has stopped, writes the same bytes the last step's seal
+    wrote (and the open after it leaves the arena as the last step left it). k = DUMP_SLOTS slots
+    and m = DUMP_TAGS packets, or all n when there are fewer: a fixed sample (sorted indices from a
+    generator seeded with DUMP_SEED), which keeps the files under 64 MB for every config."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n, stride = db.n, db.batch.stride
+    rng = np.random.default_rng(DUMP_SEED)
+    slot_idx = np.sort(rng.choice(n, DUMP_SLOTS, replace=False)) if n > DUMP_SLOTS else np.arange(n)
+    tag_idx = np.sort(rng.choice(n, DUMP_TAGS, replace=False)) if n > DUMP_TAGS else np.arange(n)
+    slots_d = torch.from_numpy(slot_idx).to(db.dev)
+    d = db.batch.desc[tag_idx]
+    tag_at = (d["dst_off"] + d["len"].astype(np.uint64)).astype(np.int64)
+    tag_d = torch.from_numpy(tag_at[:, None] + np.arange(16, dtype=np.int64)[None, :]).to(db.dev)
+    sfx = f"_rank{rank}" if rank else ""
+
+    def save(name, t):
+        a = t.cpu().numpy() if hasattr(t, "cpu") else t
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a.astype(np.float32))
+
+    save("status", status)
+    save("opened_slots", db.arena.view(n, stride)[slots_d])
+    db.seal()
+    torch.cuda.synchronize()
+    save("sealed_tags", db.arena[tag_d])
+    save("sealed_slots", db.arena.view(n, stride)[slots_d])
+    db.open()
+    torch.cuda.synchronize()
+    assert (db.status_host() == 0).all(), "open failed after --dump-outputs"
 
 
 def hbm_over_ranks(ctrl, world: int, alg_bytes: float, seal_ms: float, ndev: int) -> dict:

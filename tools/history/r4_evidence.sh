@@ -20,6 +20,6 @@ grep -v phases $OUT/queue.jsonl | cut -c1-220
 cd $R
 for c in ${CONFIGS:-0 1 2 3 4}; do
   st=20; [ $c = 4 ] && st=10
-  timeout -k 10 400 python bench.py --config $c --steps $st --warmup 5 > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err || exit $?
+  timeout -k 10 400 python bench.py --full --config $c --steps $st --warmup 5 > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err || exit $?
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); cb=d.get('cpu_baseline') or {}; print('C%d' % (int(sys.argv[2])+1), d['value'], d['ms_per_step'], 'cpu', cb.get('value'), cb.get('cores'), cb.get('value_1thread'))" $OUT/bench_c$c.json $c
 done

@@ -9,7 +9,7 @@ for r in 1 2; do
   for v in prod prio0 prio1; do
     for c in 2 4 1; do
       st=20; [ $c = 4 ] && st=10
-      env $(ab_env $v) timeout -k 10 300 python bench.py --config $c --steps $st --warmup 5 --no-cpu-baseline > $OUT/ab_${v}_c${c}_$r.json 2> $OUT/ab_${v}_c${c}_$r.err || exit $?
+      env $(ab_env $v) timeout -k 10 300 python bench.py --full --config $c --steps $st --warmup 5 --no-cpu-baseline > $OUT/ab_${v}_c${c}_$r.json 2> $OUT/ab_${v}_c${c}_$r.err || exit $?
       echo "$v C$((c+1)) run $r: $(grep -o '"value": [0-9.]*' $OUT/ab_${v}_c${c}_$r.json) $(grep -o '"kernel_ms": [0-9.]*' $OUT/ab_${v}_c${c}_$r.json)"
     done
   done

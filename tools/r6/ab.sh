@@ -10,7 +10,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     c=${cfg%%:*}; so=""; [ "$cfg" != "$c" ] && so="--shard-of ${cfg#*:}"
     for v in ${VARIANTS:-new=}; do
       name=${v%%=*}; lib=${v#*=}
-      line=$(NEB_LIB_PATH=$lib timeout -k 10 300 python bench.py --config $c $so --no-cpu-baseline ${BENCH_ARGS} 2>>$OUT.err) || { echo "FAIL $name $cfg"; exit 1; }
+      line=$(NEB_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --config $c $so --no-cpu-baseline ${BENCH_ARGS} 2>>$OUT.err) || { echo "FAIL $name $cfg"; exit 1; }
       python3 -c "
 import json,sys; d=json.loads(sys.argv[1]); r=d.get('roofline',{})
 o={'variant':sys.argv[2],'cfg':sys.argv[3],'rep':int(sys.argv[4]),'value':d['value'],'ms':d['ms_per_step'],'seal_k':r.get('kernel_ms'),'open_k':r.get('open_kernel_ms'),'call':r.get('seal_call_ms')}

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/r6e_${TAG:-a}; mkdir -p $OUT
 cp gpurun_out/pytest_gpu.log gpurun_out/bench.log gpurun_out/smoke.log $OUT/ 2>/dev/null
 run() {  # name args...
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || exit $?
+  timeout -k 10 400 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || exit $?
   cut -c1-260 $OUT/$name.json
 }
 for c in 1 2 3 4; do run bench_c$((c+1)) --config $c --steps 20 --warmup 5; done
