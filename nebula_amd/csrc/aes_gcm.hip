@@ -124,6 +124,17 @@ __device__ __forceinline__ T lds_at(const void* base, uint32_t byte_off) {
         __builtin_assume_aligned(reinterpret_cast<const char*>(base) + byte_off, sizeof(T)));
 }
 
+// One ds_read_b64. The load is volatile so that two of them off one address register stay two
+// instructions: merged into a ds_read2_b64 they would bank on (addr/4) mod 32 and cost 8 LDS cycles
+// instead of 2 + 2.
+__device__ __forceinline__ uint2 lds_b64(const void* base, uint32_t byte_off) {
+    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+    // (the LDS address space is named: a volatile access through a generic pointer stays a flat load)
+    typedef const volatile __attribute__((address_space(3))) v2u* lds_ptr;
+    const v2u v = *(lds_ptr)__builtin_assume_aligned(reinterpret_cast<const char*>(base) + byte_off, 8);
+    return make_uint2(v.x, v.y);
+}
+
 // ------------------------------------------------------------------------------------------
 // AES-256 encryption of one block per lane (little-endian column words in and out).
 // ttab: LDS, 32 copies of 256 8-byte entries, entry x of copy c at byte x*256 + c*8 holding
@@ -473,6 +484,49 @@ __device__ __forceinline__ uint4 gf_mul_full(uint4 x, uint4 acc, const uint4* ft
     return acc;
 }
 
+// The single-key kernel's Horner multiply on 5-bit windows (NEB_GHASH5=0: the nibble table above).
+#ifndef NEB_GHASH5
+#define NEB_GHASH5 1
+#endif
+// 26 windows cover x^0..x^127 (128 = 25·5 + 3): window P holds the coefficients x^(5P)..x^(5P+4),
+// its value v has MSB = x^(5P); window 25 has three coefficients, in the top bits of its value.
+constexpr int kWin5 = 26;
+// x · F where f5 (LDS) holds F5[P][v] = (v·x^5P)·H^4 (reduced) as two tables of 8-byte halves: words
+// 0-1 of position P at byte 2P*256 + 8v, words 2-3 at (2P+1)*256 + 8v. A table is one 256-byte row
+// of the LDS, so the 32 lanes of a ds_read_b64 pass read it conflict-free whatever their entries
+// (distinct entries are distinct bank pairs, equal entries one address), and no lane rotation is
+// needed. 52 ds_read_b64 at 2 array cycles against gf_mul_full's 32 ds_read_b128 at 4.
+// One address (v << 3) per window serves both halves; windows 6, 12 and 19 straddle two words.
+__device__ __forceinline__ uint4 gf_mul_full5(uint4 x, uint4 acc, const uint2* f5) {
+    const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
+    uint2 lo[kWin5], hi[kWin5];
+    auto issue = [&](int P) {
+        const int q = (5 * P) >> 5, r = (5 * P) & 31;  // the window's MSB = bit 31-r of word q
+        uint32_t w;
+        if (r > 27 && q < 3) w = __builtin_amdgcn_alignbit(xw[q], xw[q + 1], 56 - r);  // field -> bits 3-7
+        else w = r <= 24 ? xw[q] >> (24 - r) : xw[q] << (r - 24);
+        const uint32_t a = w & 0xF8u;
+        lo[P] = lds_b64(f5, (uint32_t)(2 * P) * 256u + a);
+        hi[P] = lds_b64(f5, (uint32_t)(2 * P + 1) * 256u + a);
+    };
+    // The volatile reads keep their program order, so the schedule is written out: the 8 reads of
+    // 4 windows, then their fold; the other waves cover the latency, as in gf_mul_full (2 reads,
+    // then their fold). C2 A/B over 5 rounds: steps of 2, 4 and 6 windows gave 840.7, 847.8 and
+    // 846.6 GiB/s against the nibble table's 814.8 (profiles/ghash5/ab_c2.jsonl); issuing the next
+    // step's reads before the fold gained nothing, and from 4 windows ahead on it spills.
+    constexpr int kStep = 4;
+#pragma unroll
+    for (int g = 0; g < kWin5; g += kStep) {
+#pragma unroll
+        for (int P = g; P < g + kStep && P < kWin5; P++) issue(P);
+#pragma unroll
+        for (int P = g; P < g + kStep && P < kWin5; P += 2)  // kWin5 is even: windows fold in pairs
+            acc = make_uint4(x3(acc.x, lo[P].x, lo[P + 1].x), x3(acc.y, lo[P].y, lo[P + 1].y),
+                             x3(acc.z, hi[P].x, hi[P + 1].x), x3(acc.w, hi[P].y, hi[P + 1].y));
+    }
+    return acc;
+}
+
 // x · P where ptab (LDS) holds the 8 position tables T_r[v] = v·x^(4r)·P (reduced) at byte
 // r*256 + v*16: nibble r of word q contributes T_r[v]·x^(32q), a shift by whole words, so the 32
 // lookups XOR straight into a 224-bit product that is reduced once. No shifts (the Shoup form
@@ -815,11 +869,19 @@ __device__ __forceinline__ uint4 final_perm(uint4 A, const FinalPermLanes& fp, M
 // One key per batch, LPP 4 (gcm_single_kernel): reduction-free full table of H^4 for the Horner
 // step, position tables of H, H^2, H^3, H^4 for the permuted final.
 struct GhFullPerm {
+#if NEB_GHASH5
+    const uint2* full;  // F5, the 5-bit window table of H^4 (gf_mul_full5)
+#else
     const uint4* full;
+#endif
     const void* base;  // the LDS base of FinalPermLanes::off
     FinalPermLanes fp;
     __device__ __forceinline__ uint4 horner(uint4 a, uint32_t) const {
+#if NEB_GHASH5
+        return gf_mul_full5(a, make_uint4(0, 0, 0, 0), full);
+#else
         return gf_mul_full(a, make_uint4(0, 0, 0, 0), full);
+#endif
     }
     __device__ __forceinline__ uint4 final(uint4 A, uint32_t, uint32_t) const {
         return final_perm(A, fp, [&](uint4 a, uint32_t off) { return gf_mul_pos_off(a, base, off); });
@@ -1187,10 +1249,17 @@ constexpr int kSingleWpe = 4;  // launch bound: waves per SIMD
 constexpr int kSingleThreads = kSingleWaves * kWave;
 
 struct SingleLds {
+#if NEB_GHASH5
+    uint2 full[2 * kWin5 * 32];  // 13 KiB  F5[P][v] for H^4, halves (first: its offsets fit the ds_read offset field)
+#else
     uint4 full[32 * 16];       // 8 KiB   F_p[v] for H^4 (first: its offsets fit the ds_read offset field)
+#endif
     uint4 pos1[8 * 16];        // 2 KiB   position tables of H
     uint2 ttab[2 * 256 * 32];  // 128 KiB (T0,T1) and (T2,T3) pairs, 32 copies each
     uint4 pos23[2][8 * 16];    // 4 KiB   position tables of H^2 and H^3 (the permuted final)
+#if NEB_GHASH5
+    uint4 pos4[8 * 16];        // 2 KiB   position tables of H^4 (the final's; positions 0-7 of the nibble table)
+#endif
 };
 struct SingleLdsCs : SingleLds {
     uint4 pow2[10 * 16];  // 2.5 KiB  Shoup tables of H^(2^j), j < 10 (the TX checksum correction)
@@ -1209,14 +1278,40 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
 #endif
     // the record's GHASH tables: loaded before the T-table fill and stored after it, so their
     // latency overlaps the fill's instead of following it
-    static_assert(kSingleThreads >= 512, "one full-table entry per thread");
     uint4 r_full = make_uint4(0, 0, 0, 0), r_h = make_uint4(0, 0, 0, 0), r_p = make_uint4(0, 0, 0, 0);
+#if NEB_GHASH5
+    // F5[P][v] from the record's nibble table: x^b·H^4 is its entry F_(b/4)[8 >> (b%4)], and thread
+    // t < 26·32 XORs those of the (at most five) coefficients x^(5P+j) that v = t mod 32 selects
+    static_assert(kSingleThreads >= kWin5 * 32, "one window-table entry per thread");
+    const uint32_t f5_p = tid >> 5, f5_v = tid & 31u;
+    if (tid < (uint32_t)kWin5 * 32u) {
+#pragma unroll
+        for (uint32_t j = 0; j < 5u; j++) {
+            const uint32_t b = 5u * f5_p + j, bc = min(b, 127u);
+            const uint4 c = ld_rec4(srec, kRecFull + 4u * ((bc >> 2) * 16u + (8u >> (bc & 3u))));
+            const uint32_t m = (b < 128u && ((f5_v >> (4u - j)) & 1u)) ? ~0u : 0u;
+            r_full = make_uint4(r_full.x ^ (c.x & m), r_full.y ^ (c.y & m), r_full.z ^ (c.z & m), r_full.w ^ (c.w & m));
+        }
+    }
+    if (tid < 128u) r_h = ld_rec4(srec, kRecPos1 + 4u * tid);
+    if (tid < 384u) r_p = ld_rec4(srec, (tid < 128u ? kRecPos2 : tid < 256u ? kRecPos3 : kRecFull) + 4u * (tid & 127u));
+#else
+    static_assert(kSingleThreads >= 512, "one full-table entry per thread");
     if (tid < 512u) r_full = ld_rec4(srec, kRecFull + 4u * tid);
     if (tid < 128u) r_h = ld_rec4(srec, kRecPos1 + 4u * tid);
     if (tid < 256u) r_p = ld_rec4(srec, (tid < 128u ? kRecPos2 : kRecPos3) + 4u * (tid & 127u));
+#endif
     const TLook4 T{lds.ttab, ttab4_lane_base(lane)};
     fill_ttab<2u * 256u * 32u, kSingleThreads>(lds.ttab, tid, ttab4_entry);
+#if NEB_GHASH5
+    if (tid < (uint32_t)kWin5 * 32u) {
+        lds.full[(2u * f5_p) * 32u + f5_v] = make_uint2(r_full.x, r_full.y);
+        lds.full[(2u * f5_p + 1u) * 32u + f5_v] = make_uint2(r_full.z, r_full.w);
+    }
+    if (tid >= 256u && tid < 384u) lds.pos4[tid & 127u] = r_p;
+#else
     if (tid < 512u) lds.full[tid] = r_full;
+#endif
     if (tid < 128u) lds.pos1[tid] = r_h;
     if (tid < 256u) lds.pos23[tid >> 7][tid & 127u] = r_p;
 
@@ -1229,7 +1324,11 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
     load_round_keys(srec, rks);
     __syncthreads();
     const RkRegs rk{rks};
+#if NEB_GHASH5
+    const uint32_t tab_off[4] = {(uint32_t)offsetof(SingleLds, pos4), (uint32_t)offsetof(SingleLds, pos23[1]),
+#else
     const uint32_t tab_off[4] = {(uint32_t)offsetof(SingleLds, full), (uint32_t)offsetof(SingleLds, pos23[1]),
+#endif
                                  (uint32_t)offsetof(SingleLds, pos23[0]), (uint32_t)offsetof(SingleLds, pos1)};
     const GhFullPerm gh{lds.full, &lds, final_perm_lanes(lane, tab_off)};
 
