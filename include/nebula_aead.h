@@ -36,6 +36,9 @@
  *                            receive batch (the recvmmsg flush, interface.go:381-413): window
  *                            Check → DecryptDanger → window Update, results identical to the
  *                            per-packet loop in arrival order
+ *   neb_relay_forward_batch  handleOutsideRelayPacket's ForwardingType branch (outside.go:120-130,
+ *                            :220-240): VerifyRelay, then SendVia (inside.go:442-501) in place,
+ *                            over a whole receive batch
  *   neb_queue_*              the flush points themselves (flushSendBatch interface.go:478-487,
  *                            listenOut's flush :395-400) of every routine (interface.go:320-335),
  *                            gathered into shared device batches
@@ -417,6 +420,56 @@ NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnel
                                    const neb_tx_packet* packets, uint32_t npackets, const uint8_t* in, size_t in_len,
                                    uint8_t* out, size_t out_cap, neb_tx_wire* wires, int32_t* wire_status,
                                    uint32_t max_wires, uint32_t* nwires, int32_t* packet_status, uint32_t key_hint);
+/* ---- relay forwarding: VerifyRelay, then SendVia in place ------------------------------------- */
+/* A relay node forwards every relayed packet the same way (handleOutsideRelayPacket's ForwardingType
+ * branch, outside.go:120-130 and :220-240; SendVia, inside.go:442-501): VerifyRelay with the inbound
+ * tunnel's key through its replay window, the next message counter of the outbound tunnel, a new
+ * Message/Relay header over the old one and a new tag under the outbound key where the old tag
+ * was — one packet at a time ("it would potentially be nice to batch these", outside.go:239).
+ * These calls do it for a whole receive batch. TerminalType relays (the inner packet is for this
+ * node) are not unwrapped here: the caller gives them no route and receives the inner packets in
+ * a batch of their own. */
+#define NEB_RELAY_NONE 0xFFFFFFFFu
+#define NEB_STATUS_NOT_FORWARDED 8 /* fwd_status: not a verified Message/Relay packet, or no route */
+/* Per received packet: what the caller's relay lookups found for the header's remote index
+ * (relayState.QueryRelayForByIdx, outside.go:201, then hostMap.QueryVpnAddrsRelayFor, :222; a route
+ * only for an Established ForwardingType target, :233-240). */
+typedef struct neb_relay_route {
+    uint32_t tunnel;       /* index into the tunnel array (the target HostInfo); NEB_RELAY_NONE: do not forward */
+    uint32_t remote_index; /* targetRelay.RemoteIndex, written into the new header (inside.go:462) */
+} neb_relay_route;
+/* Receive half: status[], the arena and the windows are exactly what neb_rx_open_wire_batch[_host]
+ * gives for the same pk (the gate, replay and tag statuses, other packets opened in place, all in
+ * arrival order); key_hint applies to it.
+ * Forward half, per packet i in arrival order. Eligible: status[i] == NEB_STATUS_OK, the header is
+ * Message/Relay (type 1, subtype 1) and route[i].tunnel != NEB_RELAY_NONE; every other packet gets
+ * fwd_status[i] = NEB_STATUS_NOT_FORWARDED, no further write and no counter. NEB_STATUS_BAD_KEY:
+ * route[i].tunnel >= ntunnels, or that tunnel's key_id is NEB_KEYS_MIXED, not installed, or of the
+ * other algorithm (no usable eKey, as neb_tx_seal_batch's NEB_STATUS_BAD_KEY): untouched, no counter. Otherwise the packet takes the next
+ * counter of tunnels[t]: the k-th such packet of tunnel t in arrival order gets message_counter + k
+ * (k from 1); a forgery or a replay between two valid packets takes none, as the reference
+ * allocates only after VerifyRelay returned nil. A counter >= NEB_REJECT_AFTER_MESSAGES:
+ * NEB_STATUS_EXHAUSTED, the packet untouched (prepareSendVia returns before Encode), the counter
+ * still used, as neb_tx_seal_batch does for a segment. Otherwise NEB_STATUS_OK: bytes 0..15 become
+ * header.Encode(1, Message, MessageRelay, route[i].remote_index, c), bytes len-16..len the tag of
+ * the AD-only seal under the tunnel's key with nonce c over packet[:len-16] (with the new header);
+ * the bytes in between are not written. tunnels[].message_counter advances by the counters taken
+ * (on the device for the device form, so forwarding and neb_tx_seal_batch on the same array and
+ * stream share the counters; the host form updates the caller's array).
+ * Device form: device pointers; returns once the receive is done, with the forward half enqueued
+ * on `stream`: every output is valid once `stream` is synchronized. With ntunnels == 1 the
+ * forwarding seal runs as a single-key batch. ChaCha20-Poly1305 tags are Poly1305 over the AD, as
+ * VerifyRelay's. A packet whose target key is destroyed while the batch runs may get the seal's
+ * NEB_STATUS_BAD_KEY with its header already rewritten. */
+NEB_API int neb_relay_forward_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk,
+                                    const neb_relay_route* d_route, uint32_t n, neb_tx_tunnel* d_tunnels,
+                                    uint32_t ntunnels, uint8_t* d_arena, int32_t* d_status, int32_t* d_fwd_status,
+                                    uint32_t key_hint, void* stream);
+/* The same over host memory (synchronous; arena as neb_rx_open_wire_batch_host's). */
+NEB_API int neb_relay_forward_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                                         const neb_rx_packet* pk, const neb_relay_route* route, uint32_t n,
+                                         neb_tx_tunnel* tunnels, uint32_t ntunnels, uint8_t* arena, size_t arena_len,
+                                         int32_t* status, int32_t* fwd_status, uint32_t key_hint);
 /* ---- submission queue: many threads' small flushes -> device-sized batches -------------------- */
 /* Nebula seals <= 128 packets per TX flush (overlay/batch/tx_batch.go:5, flushSendBatch
  * interface.go:465-487) and opens <= listen.batch = 64 per RX flush (main.go:181, listenOut

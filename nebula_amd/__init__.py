@@ -10,10 +10,12 @@ from ._lib import (ALG_AESGCM, ALG_CHACHAPOLY, DESC_DTYPE, KEYS_MIXED, OVERHEAD,
 from .noiseutil import (CipherAESGCM, CipherChaChaPoly, CipherState, CipherStateAESGCM, CipherStateChaChaPoly,
                         Engine, ErrMessageCounterExhausted, ErrNoCipher, ErrOpen, NewCipherState,
                         RejectAfterMessages, RejectHeadroom, Slice)
+from .relay import relay_forward_batch, relay_forward_batch_device
 
 __all__ = [
     "ALG_AESGCM", "ALG_CHACHAPOLY", "DESC_DTYPE", "KEYS_MIXED", "OVERHEAD", "REJECT_AFTER_MESSAGES",
     "NebError", "build", "CipherAESGCM", "CipherChaChaPoly", "CipherState", "CipherStateAESGCM",
     "CipherStateChaChaPoly", "Engine", "ErrMessageCounterExhausted", "ErrNoCipher", "ErrOpen",
     "NewCipherState", "RejectAfterMessages", "RejectHeadroom", "Slice", "_lib",
+    "relay_forward_batch", "relay_forward_batch_device",
 ]

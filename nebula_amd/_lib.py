@@ -36,6 +36,7 @@ STATUS_REPLAY = 4
 STATUS_INVALID = 5
 STATUS_NO_SPACE = 6
 STATUS_NOT_MESSAGE = 7
+STATUS_NOT_FORWARDED = 8  # relay forwarding: not a verified Message/Relay packet, or no route
 
 OVERHEAD = 16
 HEADER_LEN = 16
@@ -45,6 +46,7 @@ KEYS_MIXED = 0xFFFFFFFF
 # neb_set_knob (include/nebula_aead.h)
 KNOB_HOST_MODE, KNOB_SUB_BINS_FROM, KNOB_SINGLE_MAX_GRID, KNOB_RX_STRICT, KNOB_TILE_BINS_FROM = 0, 1, 2, 3, 4
 KNOB_SMALL_BATCH, KNOB_FRONT_GROUPS = 5, 6
+RELAY_NONE = 0xFFFFFFFF  # neb_relay_route.tunnel: do not forward
 RX_OWN_SOURCE = 0x80000000  # or-ed into neb_rx_packet.len: outside.go:66-74 refused the datagram
 
 # neb_desc (include/nebula_aead.h)
@@ -56,6 +58,9 @@ assert DESC_DTYPE.itemsize == 48
 # neb_rx_packet (include/nebula_aead.h): one received wire packet and its tunnel
 RX_PACKET_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("key_id", "<u4")])
 assert RX_PACKET_DTYPE.itemsize == 16
+# neb_relay_route (include/nebula_aead.h): where a relayed packet goes (RELAY_NONE: nowhere)
+RELAY_ROUTE_DTYPE = np.dtype([("tunnel", "<u4"), ("remote_index", "<u4")])
+assert RELAY_ROUTE_DTYPE.itemsize == 8
 
 # Every symbol include/nebula_aead.h declares, with (restype, argtypes).
 _vp, _u8p, _sz, _u32, _u64, _i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
@@ -110,6 +115,8 @@ SIGNATURES = {
                                     _u32]),
     "neb_rx_open_wire_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_rx_open_wire_batch": (_i, [_vp, _i, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "neb_relay_forward_batch": (_i, [_vp, _i, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "neb_relay_forward_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _vp, _u32]),
     "neb_seal_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_open_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_seal_batch_sharded": (_i, [_i, _vp, _u32, _u32]),

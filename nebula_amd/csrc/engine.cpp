@@ -1357,6 +1357,24 @@ int neb_open_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_
     return NEB_OK;
 }
 
+// Relay forwarding (window.cpp, relay.hip): the key table its plan checks the tunnels' keys against,
+// and the seal of the first *d_n (a count in device memory) of at most n descriptors on stream s.
+void neb_engine_key_table(const neb_engine* e, const uint32_t** d_keys, uint32_t* max_keys) {
+    *d_keys = e->d_keys;
+    *max_keys = e->max_keys;
+}
+int neb_seal_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
+                         uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s) {
+    if (n == 0) return NEB_OK;
+    hipError_t err = launch_batch(e, alg, 0, d_desc, n, d_arena, d_status, key_hint, s, d_n);
+    if (err != hipSuccess) {
+        set_error("batch launch", err);
+        return NEB_ERR_HIP;
+    }
+    note_use(e, key_hint, s);
+    return NEB_OK;
+}
+
 // For the submission queue (queue.cpp): a scheduler workspace of its own, and a launch of one
 // staged batch (zero-copy on pinned memory) on the queue's stream.
 void* neb_sched_space_new() { return new (std::nothrow) SchedSpace; }

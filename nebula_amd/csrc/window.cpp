@@ -37,6 +37,7 @@
 #include "host_common.hpp"
 #include "knobs.hpp"
 #include "rxwin.hpp"
+#include "relay.hpp"
 #include "hip_guard.hpp"
 #include "window_core.hpp"
 
@@ -53,6 +54,10 @@ int neb_check_batch_args(neb_engine* e, int alg, uint32_t key_hint);
 int neb_open_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
                          uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s, const uint8_t* rx,
                          void* prebinned);
+int neb_seal_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
+                         uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s);
+void neb_engine_key_table(const neb_engine* e, const uint32_t** d_keys, uint32_t* max_keys);
+int neb_key_alg(neb_engine* e, uint32_t key);
 void* neb_sched_space_new();
 void neb_sched_space_free(void* p);
 int neb_rx_sched_begin(neb_engine* e, uint32_t n, void* sched, hipStream_t s, neb::SchedWs* ws, uint32_t* max_keys);
@@ -379,6 +384,14 @@ struct neb_dwindows {
     uint32_t wire_n = 0;
     uint32_t spin_limit = neb::kRxSpinLimit;  // neb_dwindows_set_spin_limit
     void* sched = nullptr;  // mixed-key AES-GCM receives: the open's scheduler workspace (rxwin.hpp RxBin)
+    // neb_relay_forward_batch: the forward half's workspace (relay.hpp), the event after its last
+    // use and that use's stream, one pinned word for the single target tunnel's key
+    uint8_t* relay_mem = nullptr;
+    neb::RelayWs relay_ws{};
+    uint32_t relay_n = 0, relay_tun = 0;
+    hipEvent_t relay_done = nullptr;
+    hipStream_t relay_last = nullptr;
+    uint32_t* relay_key = nullptr;
 };
 
 namespace {
@@ -478,6 +491,12 @@ NEB_API int neb_dwindows_destroy(neb_dwindows* d) {
         // throughout: with the lock taken, nothing of this window set is in flight
         std::lock_guard<std::mutex> g(d->mu);
         if (d->sched) neb_sched_space_free(d->sched);
+        if (d->relay_done) {  // the forward half of the last relay batch may still be running
+            hipEventSynchronize(d->relay_done);
+            hipEventDestroy(d->relay_done);
+        }
+        if (d->relay_mem) hipFree(d->relay_mem);
+        if (d->relay_key) hipHostFree(d->relay_key);
         if (d->ws_mem) hipFree(d->ws_mem);
         if (d->wire_mem) hipFree(d->wire_mem);
         if (d->mem) hipFree(d->mem);
@@ -788,14 +807,13 @@ NEB_API int neb_rx_open_wire_batch_host(neb_engine* e, int alg, neb_window* cons
     return NEB_OK;
 }
 
-NEB_API int neb_rx_open_wire_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk, uint32_t n,
-                                   uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
-    if (!e || !d || d->e != e || (n && (!d_pk || !d_arena || !d_status))) return NEB_ERR_INVALID;
-    int rc = neb_check_batch_args(e, alg, key_hint);
-    if (rc != NEB_OK) return rc;
-    if (n == 0) return NEB_OK;
-    std::lock_guard<std::mutex> g(d->mu);
-    DeviceGuard dg(neb_engine_device_of(e));
+}  // extern "C"
+
+// neb_rx_open_wire_batch with d->mu held and the engine's device current (the relay forwarding runs
+// its forward half under the same lock)
+static int rx_open_wire_locked(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk, uint32_t n,
+                               uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
+    int rc = NEB_OK;
     hipStream_t s = (hipStream_t)stream;
     if (n > d->wire_n) {
         RX_HIP(hipStreamSynchronize(s));
@@ -812,6 +830,117 @@ NEB_API int neb_rx_open_wire_batch(neb_engine* e, int alg, neb_dwindows* d, cons
     if (rc != NEB_OK) return rc;
     RX_HIP(neb_rxdev_wire_fix(gate, d_status, n, s));
     RX_HIP(hipStreamSynchronize(s));
+    return NEB_OK;
+}
+
+// The forward half's workspace, grown as the receive's is (no allocation in the steady state); a
+// batch on another stream waits for the last one's use of it.
+static int relay_reserve(neb_dwindows* d, uint32_t n, uint32_t ntun, hipStream_t s) {
+    if (!d->relay_done)
+        RX_HIP(hipEventCreateWithFlags(&d->relay_done, hipEventDisableTiming | hipEventDisableSystemFence));
+    if (!d->relay_key) RX_HIP(hipHostMalloc((void**)&d->relay_key, sizeof(uint32_t), hipHostMallocDefault));
+    if (d->relay_mem && n <= d->relay_n && ntun <= d->relay_tun) {
+        if (d->relay_last != s) RX_HIP(hipStreamWaitEvent(s, d->relay_done, 0));
+        return NEB_OK;
+    }
+    const uint32_t nc = std::max({n, d->relay_n, 1024u}), tc = std::max({ntun, d->relay_tun, 64u});
+    size_t cub = 0;
+    const size_t bytes = neb_relay_ws_bytes(nc, tc, &cub);
+    RX_HIP(hipEventSynchronize(d->relay_done));  // the old workspace may still be in use
+    if (d->relay_mem) hipFree(d->relay_mem);
+    d->relay_mem = nullptr;
+    d->relay_n = d->relay_tun = 0;
+    RX_HIP(hipMalloc((void**)&d->relay_mem, bytes));
+    neb::relay_ws_layout(nc, tc, cub, d->relay_mem, &d->relay_ws);
+    d->relay_n = nc;
+    d->relay_tun = tc;
+    return NEB_OK;
+}
+
+extern "C" {
+
+NEB_API int neb_rx_open_wire_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk, uint32_t n,
+                                   uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
+    if (!e || !d || d->e != e || (n && (!d_pk || !d_arena || !d_status))) return NEB_ERR_INVALID;
+    int rc = neb_check_batch_args(e, alg, key_hint);
+    if (rc != NEB_OK) return rc;
+    if (n == 0) return NEB_OK;
+    std::lock_guard<std::mutex> g(d->mu);
+    DeviceGuard dg(neb_engine_device_of(e));
+    return rx_open_wire_locked(e, alg, d, d_pk, n, d_arena, d_status, key_hint, stream);
+}
+
+// ---- relay forwarding: the receive, then SendVia in place (relay.hpp, relay.hip) -----------------
+
+NEB_API int neb_relay_forward_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk,
+                                    const neb_relay_route* d_route, uint32_t n, neb_tx_tunnel* d_tunnels,
+                                    uint32_t ntunnels, uint8_t* d_arena, int32_t* d_status, int32_t* d_fwd_status,
+                                    uint32_t key_hint, void* stream) {
+    if (!e || !d || d->e != e || (n && (!d_pk || !d_route || !d_arena || !d_status || !d_fwd_status)) ||
+        (ntunnels && !d_tunnels))
+        return NEB_ERR_INVALID;
+    int rc = neb_check_batch_args(e, alg, key_hint);
+    if (rc != NEB_OK) return rc;
+    if (n == 0) return NEB_OK;
+    std::lock_guard<std::mutex> g(d->mu);
+    DeviceGuard dg(neb_engine_device_of(e));
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = relay_reserve(d, n, ntunnels, s)) != NEB_OK) return rc;
+    // one target tunnel: its key, for the single-key seal (read back while the receive runs, which
+    // ends with the stream synchronized)
+    *d->relay_key = NEB_KEYS_MIXED;
+    if (ntunnels == 1)
+        RX_HIP(hipMemcpyAsync(d->relay_key, &d_tunnels[0].key_id, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if ((rc = rx_open_wire_locked(e, alg, d, d_pk, n, d_arena, d_status, key_hint, stream)) != NEB_OK) return rc;
+    const uint32_t seal_hint = ntunnels == 1 && neb_key_alg(e, *d->relay_key) == alg ? *d->relay_key : NEB_KEYS_MIXED;
+    const uint32_t* d_keys = nullptr;
+    uint32_t max_keys = 0;
+    neb_engine_key_table(e, &d_keys, &max_keys);
+    const neb::RelayWs& ws = d->relay_ws;
+    RX_HIP(neb_relay_plan(d_pk, d_route, d_status, n, d_tunnels, ntunnels, d_keys, max_keys, alg, d_arena, d_fwd_status,
+                          &ws, s));
+    rc = neb_seal_batch_count(e, alg, ws.sub_desc, n, ws.nsub, d_arena, ws.sub_status, seal_hint, s);
+    if (rc == NEB_OK && neb_relay_fix(&ws, n, d_fwd_status, s) != hipSuccess) rc = NEB_ERR_HIP;
+    (void)hipEventRecord(d->relay_done, s);
+    d->relay_last = s;
+    return rc;
+}
+
+// The host form: the receive over the host arena, then the same per-packet rules (neb_relay_gate,
+// neb_relay_send_via) as a plain loop in arrival order, and one seal batch over the forwarded packets.
+NEB_API int neb_relay_forward_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                                         const neb_rx_packet* pk, const neb_relay_route* route, uint32_t n,
+                                         neb_tx_tunnel* tunnels, uint32_t ntunnels, uint8_t* arena, size_t arena_len,
+                                         int32_t* status, int32_t* fwd_status, uint32_t key_hint) {
+    if (!e || (n && (!route || !fwd_status)) || (ntunnels && !tunnels)) return NEB_ERR_INVALID;
+    int rc = neb_rx_open_wire_batch_host(e, alg, windows, nwindows, pk, n, arena, arena_len, status, key_hint);
+    if (rc != NEB_OK || n == 0) return rc;
+    std::vector<neb_desc> desc;
+    std::vector<uint32_t> map;
+    for (uint32_t i = 0; i < n; i++) {
+        uint8_t* p = arena + pk[i].off;
+        int32_t st = neb_relay_gate(status[i], p, route[i], tunnels, ntunnels,
+                                    [&](uint32_t key) { return neb_key_alg(e, key) == alg; });
+        if (st == NEB_STATUS_OK) {
+            neb_tx_tunnel& t = tunnels[route[i].tunnel];
+            uint32_t hdr[4];
+            neb_desc dd;
+            st = neb_relay_send_via(pk[i], route[i].remote_index, t.key_id, ++t.message_counter, hdr, &dd);
+            if (st == NEB_STATUS_OK) {
+                std::memcpy(p, hdr, 16);
+                desc.push_back(dd);
+                map.push_back(i);
+            }
+        }
+        fwd_status[i] = st;
+    }
+    if (desc.empty()) return NEB_OK;
+    std::vector<int32_t> sub(desc.size(), NEB_STATUS_OK);
+    const uint32_t seal_hint = ntunnels == 1 ? tunnels[0].key_id : NEB_KEYS_MIXED;
+    rc = neb_seal_batch_host(e, alg, desc.data(), (uint32_t)desc.size(), arena, arena_len, sub.data(), seal_hint);
+    if (rc != NEB_OK) return rc;
+    for (size_t j = 0; j < sub.size(); j++)
+        if (sub[j] != NEB_STATUS_OK) fwd_status[map[j]] = sub[j];
     return NEB_OK;
 }
 
