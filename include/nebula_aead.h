@@ -39,6 +39,12 @@
  *   neb_relay_forward_batch  handleOutsideRelayPacket's ForwardingType branch (outside.go:120-130,
  *                            :220-240): VerifyRelay, then SendVia (inside.go:442-501) in place,
  *                            over a whole receive batch
+ *   neb_rx_coalesce_batch    MultiCoalescer.Commit / Flush (overlay/batch/multi_coalesce.go:67-133) over a
+ *                            whole opened receive batch: the (epoch, counter) sort, the TCP / UDP
+ *                            coalescers (tcp_coalesce.go, udp_coalesce.go), Passthrough, and the
+ *                            virtio header of every TUN write (overlay/tio/tio_gso_linux.go:280-404);
+ *                            neb_rx_plain_from_wire is handleOutsideMessagePacket's hand-over
+ *                            (outside.go:145-149, :474-479)
  *   neb_queue_*              the flush points themselves (flushSendBatch interface.go:478-487,
  *                            listenOut's flush :395-400) of every routine (interface.go:320-335),
  *                            gathered into shared device batches
@@ -154,7 +160,9 @@ enum {
                                    * NEB_KNOB_FRONT_GROUPS groups per chunk (default 48; 0: never) */
     NEB_KNOB_FRONT_GROUPS = 6,    /* NEB_FRONT_GROUPS: the 16-packet groups per front chunk of the short size
                                    * classes in such a batch at most (default 1; the classes' own: up to 8) */
-    NEB_KNOB_COUNT = 7
+    NEB_KNOB_COALESCE_HASH_BITS = 7, /* NEB_COALESCE_HASH_BITS: the device coalescer keeps this many bits of its
+                                   * flow hash (default 32; tests force collisions with fewer) */
+    NEB_KNOB_COUNT = 8
 };
 NEB_API int neb_set_knob(int knob, int64_t value);
 NEB_API int64_t neb_get_knob(int knob); /* -1 for an unknown knob */
@@ -470,6 +478,76 @@ NEB_API int neb_relay_forward_batch_host(neb_engine* e, int alg, neb_window* con
                                          const neb_rx_packet* pk, const neb_relay_route* route, uint32_t n,
                                          neb_tx_tunnel* tunnels, uint32_t ntunnels, uint8_t* arena, size_t arena_len,
                                          int32_t* status, int32_t* fwd_status, uint32_t key_hint);
+/* ---- receive: opened packets -> TUN writes (TSO / USO superpackets) ---------------------------- */
+/* What the reference does between the open and the TUN write: MultiCoalescer.Commit per packet, then
+ * Flush (overlay/batch/multi_coalesce.go): sort by (epoch, counter), coalesce in-flow TCP / UDP runs
+ * into superpackets, pass everything else through, and give every write its virtio_net_hdr. */
+#define NEB_VNET_F_DATA_VALID 2
+#define NEB_PLAIN_PARSED 1   /* proto / ip_hdr_len / FRAG_ANY are the caller's firewall parse
+                                (firewall.ParsedPacket); else they are derived as newPacket does */
+#define NEB_PLAIN_FRAG_ANY 2 /* ParsedPacket.FragAny (with NEB_PLAIN_PARSED) */
+#define NEB_PLAIN_SKIP 4     /* not committed (firewall drop, not a data message, not opened) */
+typedef struct neb_plain_packet { /* one MultiCoalescer.Commit */
+    uint64_t off;     /* the plaintext IP packet in the input arena */
+    uint64_t epoch;   /* SortKey.Epoch */
+    uint64_t counter; /* SortKey.Counter */
+    uint32_t len;
+    uint16_t ip_hdr_len;
+    uint8_t proto;
+    uint8_t flags; /* NEB_PLAIN_* */
+} neb_plain_packet;
+typedef struct neb_tun_write { /* one write to the TUN, in the reference's emission order */
+    uint64_t out_off; /* 16-byte aligned, in the output arena */
+    uint32_t len;
+    uint32_t first; /* input index of the verbatim packet / the chain's seed */
+    uint16_t nseg;  /* packets it carries (1 for verbatim) */
+    uint8_t vnet_flags, gso_type;
+    uint16_t hdr_len, gso_size, csum_start, csum_offset;
+    uint8_t lane; /* 0 TCP, 1 UDP, 2 passthrough */
+    uint8_t reserved[3];
+} neb_tun_write;
+#define NEB_COALESCE_TCP 1 /* the TUN accepts TSO writes (tio.Capabilities.TSO) */
+#define NEB_COALESCE_UDP 2 /* ... USO */
+#define NEB_WRITE_NONE 0xFFFFFFFFu
+/* MultiCoalescer.Flush over the records without NEB_PLAIN_SKIP.
+ * A record whose derived parse (newPacket, outside.go:320-472) fails, or an empty packet, is dropped:
+ * pkt_status NEB_STATUS_INVALID, it takes part in nothing. The others are sorted by (epoch, counter),
+ * ties by input index. Protocol 6 goes to the TCP lane if lanes & NEB_COALESCE_TCP, 17 to the UDP lane
+ * if lanes & NEB_COALESCE_UDP, everything else to passthrough. Writes come in the reference's order:
+ * the TCP lane's slots in creation order (the sorted position of the verbatim packet or the seed),
+ * then the UDP lane's, then the passthrough packets in sorted order. A verbatim slot or a chain that
+ * stayed at one segment is the whole input packet, untrimmed, with vnet_flags DATA_VALID and every
+ * other field 0. A chain of >= 2 segments is the seed's hdr_len header bytes patched as flushSlot
+ * does (lengths, IPv4 header checksum, the folded pseudo-header sum in the L4 checksum field, PSH
+ * of an appended segment or-ed in) followed by the trimmed payloads in chain order, with NEEDS_CSUM,
+ * gso_type TCPV4 / TCPV6 / UDP_L4, hdr_len, gso_size = the seed's payload length, csum_start = the
+ * IP header length and csum_offset 16 / 6. The input arena is only read (the reference patches the
+ * seed in place; this call does not). Writes are placed in order at 16-byte aligned offsets; the
+ * longest prefix that fits out_cap and max_writes is emitted and counted in *nwrites, the packets of
+ * the writes cut off get NEB_STATUS_NO_SPACE. pkt_write[i] is the write that carries packet i or
+ * NEB_WRITE_NONE; pkt_status[i] is NEB_STATUS_OK, _INVALID, _NO_SPACE or, for a skipped record,
+ * NEB_STATUS_NOT_MESSAGE. Flow identity is the full 38-byte key {src, dst, sport, dport, family}.
+ * Device pointers; asynchronous on `stream`. */
+NEB_API int neb_rx_coalesce_batch(neb_engine* e, const neb_plain_packet* d_plain, uint32_t n, const uint8_t* d_in,
+                                  uint8_t* d_out, size_t out_cap, neb_tun_write* d_writes, uint32_t max_writes,
+                                  uint32_t* d_nwrites, uint32_t* d_pkt_write, int32_t* d_pkt_status, uint32_t lanes,
+                                  void* stream);
+/* The same over host memory, on the CPU: the plain sequential algorithm, no engine and no GPU needed
+ * (one routine's 64-packet flush). Every record is checked against in_len first (NEB_ERR_INVALID:
+ * nothing written). */
+NEB_API int neb_rx_coalesce_batch_host(const neb_plain_packet* plain, uint32_t n, const uint8_t* in, size_t in_len,
+                                       uint8_t* out, size_t out_cap, neb_tun_write* writes, uint32_t max_writes,
+                                       uint32_t* nwrites, uint32_t* pkt_write, int32_t* pkt_status, uint32_t lanes);
+/* A finished neb_rx_open_wire_batch as commit records: packet i is committed iff status[i] ==
+ * NEB_STATUS_OK, its header is type Message (1), subtype None (0) (outside.go:145-149) and key_id <
+ * nepoch; then off = pk.off + 16, len = pk.len - 32, counter = header bytes 8:16, epoch =
+ * epoch[key_id], flags 0 (the parse is derived). Every other packet gets NEB_PLAIN_SKIP. */
+NEB_API int neb_rx_plain_from_wire(neb_engine* e, const neb_rx_packet* d_pk, const int32_t* d_status,
+                                   const uint64_t* d_epoch, uint32_t nepoch, uint32_t n, const uint8_t* d_arena,
+                                   neb_plain_packet* d_plain, void* stream);
+NEB_API int neb_rx_plain_from_wire_host(const neb_rx_packet* pk, const int32_t* status, const uint64_t* epoch,
+                                        uint32_t nepoch, uint32_t n, const uint8_t* arena, size_t arena_len,
+                                        neb_plain_packet* plain);
 /* ---- submission queue: many threads' small flushes -> device-sized batches -------------------- */
 /* Nebula seals <= 128 packets per TX flush (overlay/batch/tx_batch.go:5, flushSendBatch
  * interface.go:465-487) and opens <= listen.batch = 64 per RX flush (main.go:181, listenOut

@@ -10,6 +10,7 @@ from ._lib import (ALG_AESGCM, ALG_CHACHAPOLY, DESC_DTYPE, KEYS_MIXED, OVERHEAD,
 from .noiseutil import (CipherAESGCM, CipherChaChaPoly, CipherState, CipherStateAESGCM, CipherStateChaChaPoly,
                         Engine, ErrMessageCounterExhausted, ErrNoCipher, ErrOpen, NewCipherState,
                         RejectAfterMessages, RejectHeadroom, Slice)
+from .outside import MultiCoalescer, coalesce_batch_device, coalesce_batch_host, receive
 from .relay import relay_forward_batch, relay_forward_batch_device
 
 __all__ = [
@@ -18,4 +19,5 @@ __all__ = [
     "CipherStateChaChaPoly", "Engine", "ErrMessageCounterExhausted", "ErrNoCipher", "ErrOpen",
     "NewCipherState", "RejectAfterMessages", "RejectHeadroom", "Slice", "_lib",
     "relay_forward_batch", "relay_forward_batch_device",
+    "MultiCoalescer", "coalesce_batch_host", "coalesce_batch_device", "receive",
 ]

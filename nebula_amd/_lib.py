@@ -46,6 +46,7 @@ KEYS_MIXED = 0xFFFFFFFF
 # neb_set_knob (include/nebula_aead.h)
 KNOB_HOST_MODE, KNOB_SUB_BINS_FROM, KNOB_SINGLE_MAX_GRID, KNOB_RX_STRICT, KNOB_TILE_BINS_FROM = 0, 1, 2, 3, 4
 KNOB_SMALL_BATCH, KNOB_FRONT_GROUPS = 5, 6
+KNOB_COALESCE_HASH_BITS = 7  # the device coalescer's flow hash keeps this many bits (tests: collisions)
 RELAY_NONE = 0xFFFFFFFF  # neb_relay_route.tunnel: do not forward
 RX_OWN_SOURCE = 0x80000000  # or-ed into neb_rx_packet.len: outside.go:66-74 refused the datagram
 
@@ -61,6 +62,20 @@ assert RX_PACKET_DTYPE.itemsize == 16
 # neb_relay_route (include/nebula_aead.h): where a relayed packet goes (RELAY_NONE: nowhere)
 RELAY_ROUTE_DTYPE = np.dtype([("tunnel", "<u4"), ("remote_index", "<u4")])
 assert RELAY_ROUTE_DTYPE.itemsize == 8
+
+# neb_plain_packet (include/nebula_aead.h): one MultiCoalescer.Commit
+PLAIN_PARSED, PLAIN_FRAG_ANY, PLAIN_SKIP = 1, 2, 4
+PLAIN_PACKET_DTYPE = np.dtype([("off", "<u8"), ("epoch", "<u8"), ("counter", "<u8"), ("len", "<u4"),
+                               ("ip_hdr_len", "<u2"), ("proto", "u1"), ("flags", "u1")])
+assert PLAIN_PACKET_DTYPE.itemsize == 32
+# neb_tun_write (include/nebula_aead.h): one write to the TUN with its virtio_net_hdr fields
+TUN_WRITE_DTYPE = np.dtype([("out_off", "<u8"), ("len", "<u4"), ("first", "<u4"), ("nseg", "<u2"),
+                            ("vnet_flags", "u1"), ("gso_type", "u1"), ("hdr_len", "<u2"), ("gso_size", "<u2"),
+                            ("csum_start", "<u2"), ("csum_offset", "<u2"), ("lane", "u1"), ("reserved", "u1", (3,))])
+assert TUN_WRITE_DTYPE.itemsize == 32
+COALESCE_TCP, COALESCE_UDP = 1, 2
+WRITE_NONE = 0xFFFFFFFF
+VNET_F_NEEDS_CSUM, VNET_F_DATA_VALID = 1, 2
 
 # Every symbol include/nebula_aead.h declares, with (restype, argtypes).
 _vp, _u8p, _sz, _u32, _u64, _i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
@@ -117,6 +132,10 @@ SIGNATURES = {
     "neb_rx_open_wire_batch": (_i, [_vp, _i, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "neb_relay_forward_batch": (_i, [_vp, _i, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "neb_relay_forward_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _vp, _u32]),
+    "neb_rx_coalesce_batch": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "neb_rx_coalesce_batch_host": (_i, [_vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32]),
+    "neb_rx_plain_from_wire": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "neb_rx_plain_from_wire_host": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
     "neb_seal_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_open_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_seal_batch_sharded": (_i, [_i, _vp, _u32, _u32]),

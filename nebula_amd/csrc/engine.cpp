@@ -35,6 +35,7 @@
 #include "sched.hpp"
 #include "timing.hpp"
 #include "tx.hpp"
+#include "coalesce.hpp"
 
 // n keys (32 B each, mapped host memory) into the records of key slots slots[0..n): one launch
 extern "C" hipError_t neb_gcm_key_setup(const uint8_t* keys, const uint32_t* slots, uint32_t n, uint32_t* table,
@@ -200,6 +201,16 @@ struct TxSpace {
     std::mutex mu;
 };
 
+// Device workspace of the receive coalescer (coalesce.hpp).
+struct CoSpace {
+    uint8_t* mem = nullptr;
+    uint32_t n_cap = 0;
+    neb::CoWs ws{};
+    hipEvent_t done = nullptr;
+    StreamTag last;
+    std::mutex mu;
+};
+
 // Per-packet CipherState calls (neb_encrypt_danger / neb_decrypt_danger) and key installs share a
 // fixed pool of kPktSlots slots per engine: a stream and pinned, mapped staging the kernel reads
 // and writes in place ([desc 64 B | status 64 B | aad | payload + tag]). The box grants a process 4
@@ -313,6 +324,7 @@ struct neb_engine {
 
     SchedSpace sched;
     TxSpace tx;
+    CoSpace co;
 
     // Pipelined batched receive (window.cpp): each chunk's open on a stream (and mixed-key
     // workspace) of its own, so consecutive chunks overlap on the device; descriptors and statuses
@@ -360,6 +372,8 @@ int64_t neb::knob(int k) {
         g_knobs[NEB_KNOB_SMALL_BATCH] = sb2 ? (int64_t)std::strtoull(sb2, nullptr, 10) : (int64_t)neb::kSmallBatchPerWave;
         const char* fg = std::getenv("NEB_FRONT_GROUPS");
         g_knobs[NEB_KNOB_FRONT_GROUPS] = fg ? (int64_t)std::strtoull(fg, nullptr, 10) : (int64_t)neb::kSmallBatchGroups;
+        const char* hb = std::getenv("NEB_COALESCE_HASH_BITS");
+        g_knobs[NEB_KNOB_COALESCE_HASH_BITS] = hb ? std::atoll(hb) : 32;
         return true;
     }();
     (void)init;
@@ -618,6 +632,8 @@ NEB_API int neb_engine_destroy(neb_engine* e) {
     if (e->tx.done) { hipEventSynchronize(e->tx.done); hipEventDestroy(e->tx.done); }
     if (e->tx.mem) hipFree(e->tx.mem);
     if (e->tx.d_io) hipFree(e->tx.d_io);
+    if (e->co.done) { hipEventSynchronize(e->co.done); hipEventDestroy(e->co.done); }
+    if (e->co.mem) hipFree(e->co.mem);
     for (auto& r : e->rx.slot) {
         if (r.stream) { hipStreamSynchronize(r.stream); hipStreamDestroy(r.stream); }
         if (r.ev) hipEventDestroy(r.ev);
@@ -1927,6 +1943,66 @@ NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnel
         HIP_TRY(hipStreamSynchronize(s));
     }
     *nwires = nw;
+    return NEB_OK;
+}
+
+// ---- receive coalescer (coalesce.hip) -----------------------------------------------------------
+
+static hipError_t co_reserve(neb_engine* e, uint32_t n) {
+    CoSpace& co = e->co;
+    if (!co.done) {
+        hipError_t err = hipEventCreateWithFlags(&co.done, hipEventDisableTiming | hipEventDisableSystemFence);
+        if (err != hipSuccess) return err;
+    }
+    if (co.mem && n <= co.n_cap) return hipSuccess;
+    const uint32_t nc = std::max({n, co.n_cap, 1024u});
+    size_t cub = 0;
+    const size_t bytes = neb_co_ws_bytes(nc, &cub);
+    hipError_t err = hipEventSynchronize(co.done);  // the old workspace may still be in use
+    if (err != hipSuccess) return err;
+    if (co.mem) hipFree(co.mem);
+    co.mem = nullptr;
+    co.n_cap = 0;
+    err = hipMalloc((void**)&co.mem, bytes);
+    if (err != hipSuccess) return err;
+    neb::co_ws_layout(nc, cub, co.mem, &co.ws);
+    co.n_cap = nc;
+    return hipSuccess;
+}
+
+NEB_API int neb_rx_coalesce_batch(neb_engine* e, const neb_plain_packet* d_plain, uint32_t n, const uint8_t* d_in,
+                                  uint8_t* d_out, size_t out_cap, neb_tun_write* d_writes, uint32_t max_writes,
+                                  uint32_t* d_nwrites, uint32_t* d_pkt_write, int32_t* d_pkt_status, uint32_t lanes,
+                                  void* stream) {
+    if (!e || !d_nwrites || (n && (!d_plain || !d_in || !d_pkt_write || !d_pkt_status)) ||
+        (max_writes && !d_writes) || (out_cap && !d_out) || n > 0x7FFFFFFFu ||
+        (lanes & ~(uint32_t)(NEB_COALESCE_TCP | NEB_COALESCE_UDP)))
+        return NEB_ERR_INVALID;
+    DeviceGuard dg(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_nwrites, 0, sizeof(uint32_t), s));
+        return NEB_OK;
+    }
+    const int64_t hb = neb::knob(NEB_KNOB_COALESCE_HASH_BITS);
+    std::lock_guard<std::mutex> g(e->co.mu);
+    CoSpace& co = e->co;
+    HIP_TRY(co_reserve(e, n));
+    if (!co.last.same(s)) HIP_TRY(hipStreamWaitEvent(s, co.done, 0));
+    HIP_TRY(neb_co_run(d_plain, n, d_in, d_out, out_cap, d_writes, max_writes, d_nwrites, d_pkt_write, d_pkt_status,
+                       lanes, hb < 0 ? 0u : hb > 32 ? 32u : (uint32_t)hb, &co.ws, s));
+    HIP_TRY(hipEventRecord(co.done, s));
+    co.last.set(s);
+    return NEB_OK;
+}
+
+NEB_API int neb_rx_plain_from_wire(neb_engine* e, const neb_rx_packet* d_pk, const int32_t* d_status,
+                                   const uint64_t* d_epoch, uint32_t nepoch, uint32_t n, const uint8_t* d_arena,
+                                   neb_plain_packet* d_plain, void* stream) {
+    if (!e || (n && (!d_pk || !d_status || !d_arena || !d_plain)) || (nepoch && !d_epoch)) return NEB_ERR_INVALID;
+    if (n == 0) return NEB_OK;
+    DeviceGuard dg(e->device);
+    HIP_TRY(neb_co_plain_from_wire(d_pk, d_status, d_epoch, nepoch, n, d_arena, d_plain, (hipStream_t)stream));
     return NEB_OK;
 }
 

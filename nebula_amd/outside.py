@@ -1,0 +1,163 @@
+"""The receive side after the open (neb_rx_coalesce_batch[_host], neb_rx_plain_from_wire[_host],
+include/nebula_aead.h): MultiCoalescer's Commit / Flush (overlay/batch/multi_coalesce.go:67-133) for a
+whole batch — sort by (epoch, counter), coalesce in-flow TCP / UDP runs into TSO / USO superpackets,
+pass the rest through, and give every TUN write its virtio_net_hdr fields.
+
+The host form runs on the CPU (one routine's 64-packet flush); the device form keeps a batch that
+neb_rx_open_wire_batch opened on the device there: receive() composes the two with
+neb_rx_plain_from_wire in between."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from . import _lib as L
+from .connection_state import DeviceWindows, rx_open_wire_batch_device
+
+_vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+
+
+def coalesce_batch_host(plain: np.ndarray, arena: np.ndarray, lanes: int = L.COALESCE_TCP | L.COALESCE_UDP,
+                        out_cap: Optional[int] = None, max_writes: Optional[int] = None):
+    """neb_rx_coalesce_batch_host. plain: PLAIN_PACKET_DTYPE records over `arena` (uint8, only read).
+    Returns (writes[:nwrites] as TUN_WRITE_DTYPE, out arena, pkt_write, pkt_status)."""
+    plain = np.ascontiguousarray(plain, dtype=L.PLAIN_PACKET_DTYPE)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    n = len(plain)
+    if out_cap is None:
+        out_cap = int(((plain["len"].astype(np.int64) + 15) & ~15).sum()) if n else 0
+    if max_writes is None:
+        max_writes = n
+    out = np.zeros(max(out_cap, 1), np.uint8)
+    writes = np.zeros(max(max_writes, 1), L.TUN_WRITE_DTYPE)
+    nw = C.c_uint32(0)
+    pw = np.full(max(n, 1), L.WRITE_NONE, np.uint32)
+    ps = np.full(max(n, 1), -1, np.int32)
+    rc = L.lib().neb_rx_coalesce_batch_host(_vp(plain), n, _vp(arena), arena.nbytes, _vp(out), out_cap, _vp(writes),
+                                            max_writes, C.byref(nw), _vp(pw), _vp(ps), lanes)
+    L.check(rc, "neb_rx_coalesce_batch_host")
+    return writes[:nw.value], out, pw[:n], ps[:n]
+
+
+def coalesce_batch_device(engine, d_plain, d_in, d_out, d_writes, d_nwrites, d_pkt_write, d_pkt_status,
+                          lanes: int = L.COALESCE_TCP | L.COALESCE_UDP, stream=None) -> None:
+    """neb_rx_coalesce_batch over torch tensors on the engine's device: d_plain uint8 of
+    PLAIN_PACKET_DTYPE records, d_in / d_out uint8 arenas (out_cap = d_out.numel()), d_writes uint8 of
+    TUN_WRITE_DTYPE records (max_writes = its capacity), d_nwrites one uint32 (as int32), d_pkt_write
+    and d_pkt_status int32 per packet. Asynchronous on the stream (torch's current one by default)."""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    n = d_plain.numel() // L.PLAIN_PACKET_DTYPE.itemsize
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = L.lib().neb_rx_coalesce_batch(engine.handle, p(d_plain), n, p(d_in), p(d_out), d_out.numel(), p(d_writes),
+                                       d_writes.numel() // L.TUN_WRITE_DTYPE.itemsize, p(d_nwrites), p(d_pkt_write),
+                                       p(d_pkt_status), lanes, C.c_void_p(s))
+    L.check(rc, "neb_rx_coalesce_batch")
+
+
+def plain_from_wire_host(packets: np.ndarray, status: np.ndarray, epoch: np.ndarray, arena: np.ndarray) -> np.ndarray:
+    """neb_rx_plain_from_wire_host: the commit records of a finished rx_open_wire_batch."""
+    pk = np.ascontiguousarray(packets, dtype=L.RX_PACKET_DTYPE)
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    ep = np.ascontiguousarray(epoch, dtype=np.uint64)
+    plain = np.zeros(max(len(pk), 1), L.PLAIN_PACKET_DTYPE)
+    rc = L.lib().neb_rx_plain_from_wire_host(_vp(pk), _vp(st), _vp(ep), len(ep), len(pk), _vp(arena), arena.nbytes,
+                                             _vp(plain))
+    L.check(rc, "neb_rx_plain_from_wire_host")
+    return plain[:len(pk)]
+
+
+def plain_from_wire_device(engine, d_packets, d_status, d_epoch, d_arena, d_plain, stream=None) -> None:
+    """neb_rx_plain_from_wire over torch tensors (d_epoch: int64 holding the uint64 epochs)."""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    n = d_packets.numel() // L.RX_PACKET_DTYPE.itemsize
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = L.lib().neb_rx_plain_from_wire(engine.handle, p(d_packets), p(d_status), p(d_epoch), d_epoch.numel(), n,
+                                        p(d_arena), p(d_plain), C.c_void_p(s))
+    L.check(rc, "neb_rx_plain_from_wire")
+
+
+class TunWrite:
+    """One write to the TUN: the virtio_net_hdr fields and the bytes."""
+
+    def __init__(self, rec, data: bytes):
+        self.flags, self.gso_type = int(rec["vnet_flags"]), int(rec["gso_type"])
+        self.hdr_len, self.gso_size = int(rec["hdr_len"]), int(rec["gso_size"])
+        self.csum_start, self.csum_offset = int(rec["csum_start"]), int(rec["csum_offset"])
+        self.first, self.nseg, self.lane = int(rec["first"]), int(rec["nseg"]), int(rec["lane"])
+        self.data = data
+
+
+class MultiCoalescer:
+    """batch.MultiCoalescer's surface: Commit stages a plaintext packet with its sort key and the
+    firewall's parse (None: derived as newPacket does), Flush returns the TUN writes in the
+    reference's order. engine=None runs the host form; with an engine the batch goes through the
+    device form."""
+
+    def __init__(self, tso: bool = True, uso: bool = True, engine=None):
+        self.lanes = (L.COALESCE_TCP if tso else 0) | (L.COALESCE_UDP if uso else 0)
+        self.engine = engine
+        self._pk: List[Tuple[bytes, int, int, Optional[Tuple[int, bool, int]]]] = []
+
+    def Commit(self, pkt: bytes, epoch: int, counter: int, pp: Optional[Tuple[int, bool, int]] = None) -> None:
+        """pp: (Protocol, FragAny, IPHdrLen) of firewall.ParsedPacket."""
+        self._pk.append((bytes(pkt), epoch, counter, pp))
+
+    def _stage(self):
+        plain = np.zeros(len(self._pk), L.PLAIN_PACKET_DTYPE)
+        parts, off = [], 0
+        for i, (d, ep, ctr, pp) in enumerate(self._pk):
+            plain[i] = (off, ep, ctr, len(d), pp[2] if pp else 0, pp[0] if pp else 0,
+                        (L.PLAIN_PARSED | (L.PLAIN_FRAG_ANY if pp[1] else 0)) if pp else 0)
+            parts.append(d)
+            off += len(d)
+        return plain, np.frombuffer(b"".join(parts) + b"\0", np.uint8).copy()
+
+    def Flush(self) -> List[TunWrite]:
+        if not self._pk:
+            return []
+        plain, arena = self._stage()
+        self._pk = []
+        if self.engine is None:
+            writes, out, _, _ = coalesce_batch_host(plain, arena, self.lanes)
+        else:
+            import torch
+
+            dev = torch.device("cuda", self.engine.device)
+            n = len(plain)
+            cap = int(((plain["len"].astype(np.int64) + 15) & ~15).sum()) + 16
+            t = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev)  # noqa: E731
+            d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
+            d_writes = torch.zeros(n * L.TUN_WRITE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            d_nw = torch.zeros(1, dtype=torch.int32, device=dev)
+            d_pw = torch.zeros(n, dtype=torch.int32, device=dev)
+            d_ps = torch.zeros(n, dtype=torch.int32, device=dev)
+            d_plain, d_in = t(plain), t(arena)
+            coalesce_batch_device(self.engine, d_plain, d_in, d_out, d_writes, d_nw, d_pw, d_ps, self.lanes)
+            torch.cuda.synchronize(dev)
+            writes = d_writes.cpu().numpy().view(L.TUN_WRITE_DTYPE)[:int(d_nw.item())]
+            out = d_out.cpu().numpy()
+        return [TunWrite(w, out[int(w["out_off"]):int(w["out_off"]) + int(w["len"])].tobytes()) for w in writes]
+
+
+def receive(engine, alg: int, windows: DeviceWindows, d_packets, d_arena, d_status, d_epoch, d_plain, d_out,
+            d_writes, d_nwrites, d_pkt_write, d_pkt_status, lanes: int = L.COALESCE_TCP | L.COALESCE_UDP,
+            key_hint: int = L.KEYS_MIXED, stream=None) -> None:
+    """Wire packets to TUN writes on the device: neb_rx_open_wire_batch (the gate, the replay windows,
+    Decrypt / VerifyRelay) -> neb_rx_plain_from_wire (opened data messages become commit records,
+    epoch = d_epoch[key_id]) -> neb_rx_coalesce_batch. The caller marks firewall drops by or-ing
+    PLAIN_SKIP into d_plain's flags between the last two steps if it filters; this composition commits
+    every opened data message. The outputs are valid once the stream is synchronized."""
+    rx_open_wire_batch_device(engine, alg, windows, d_packets, d_arena, d_status, key_hint, stream)
+    plain_from_wire_device(engine, d_packets, d_status, d_epoch, d_arena, d_plain, stream)
+    coalesce_batch_device(engine, d_plain, d_arena, d_out, d_writes, d_nwrites, d_pkt_write, d_pkt_status, lanes,
+                          stream)
+
+
+__all__ = ["MultiCoalescer", "TunWrite", "coalesce_batch_host", "coalesce_batch_device", "plain_from_wire_host",
+           "plain_from_wire_device", "receive"]
