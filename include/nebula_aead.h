@@ -27,11 +27,14 @@
  *   neb_window_*             nebula.Bits, the anti-replay window: NewBits bits.go:28-50,
  *                            Check :134-150, Update :152-262, its lost / duplicate / out-of-window
  *                            counters (:23-25, network.packets.{lost,duplicate,out_of_window})
- *   neb_tx_seal_batch        sendInsideMessage (inside.go:154-240) over a batch of TUN reads:
+ *   neb_tx_seal_batch        sendInsideMessage's direct branch (inside.go:154-177, :225-239) over a
+ *                            batch of TUN reads:
  *                            decodeRead (overlay/tio/tio_gso_linux.go:231-280), SegmentSuperpacket
  *                            (overlay/tio/tun_linux_offload.go:46-60, virtio/segment_linux.go),
  *                            sendInsideEncrypt (inside.go:123-146) into SendBatch slots
  *                            (overlay/batch/tx_batch.go:15-59)
+ *   neb_tx_seal_via_batch    the same with its relay branch (inside.go:178-223): the segment
+ *                            sealed under the target's key, then prepareSendVia (:442-501)
  *   neb_rx_open_batch_host   ConnectionState.Decrypt (connection_state.go:99-119) over a whole
  *                            receive batch (the recvmmsg flush, interface.go:381-413): window
  *                            Check → DecryptDanger → window Update, results identical to the
@@ -405,9 +408,11 @@ typedef struct neb_tx_wire {
     uint32_t len;     /* 16 + segment + 16 */
     uint32_t packet;  /* index of the neb_tx_packet it came from */
     uint32_t segment; /* segment index within that packet */
-    uint32_t reserved;
+    uint32_t reserved; /* neb_tx_seal_via_batch: NEB_TX_WIRE_VIA for a wire sent through a relay, else 0 */
 } neb_tx_wire;
-/* sendInsideMessage (inside.go:154-240) for a whole batch of TUN reads: every packet is validated
+#define NEB_TX_WIRE_VIA 1
+/* sendInsideMessage's direct branch (inside.go:154-177 and :225-239; the relay branch :178-223 is
+ * neb_tx_seal_via_batch below) for a whole batch of TUN reads: every packet is validated
  * and segmented exactly as decodeRead + SegmentSuperpacket do (TSO: per-segment seq, CWR/FIN/PSH,
  * IPv4 ID and lengths, IPv4 and TCP checksums; USO: lengths and UDP checksum; plain packets with
  * NEEDS_CSUM get FinishChecksum), each segment takes the next counter of its tunnel in batch order,
@@ -478,6 +483,54 @@ NEB_API int neb_relay_forward_batch_host(neb_engine* e, int alg, neb_window* con
                                          const neb_rx_packet* pk, const neb_relay_route* route, uint32_t n,
                                          neb_tx_tunnel* tunnels, uint32_t ntunnels, uint8_t* arena, size_t arena_len,
                                          int32_t* status, int32_t* fwd_status, uint32_t key_hint);
+/* ---- transmit through a relay: seal, then SendVia, in one call ---------------------------------- */
+/* sendInsideMessage with its relay branch (inside.go:178-223: `!remote.IsValid()`, the target is
+ * reached only through a relay): neb_tx_seal_batch[_host] plus via[0..ntunnels). via[t].tunnel is
+ * the index, in the same tunnel array, of the relay tunnel of target tunnel t (relayHostInfo of
+ * QueryVpnAddrsRelayFor, inside.go:183-198), via[t].remote_index is relay.RemoteIndex
+ * (inside.go:462); NEB_RELAY_NONE: t is sent directly. via == NULL: every tunnel is direct, the
+ * call is neb_tx_seal_batch.
+ * Per TUN read i in batch order, t = packets[i].tunnel, v = via[t].tunnel: validation, BAD_KEY for
+ * t and the fitting prefix (NO_SPACE) as neb_tx_seal_batch, except that a via segment's slot is
+ * (16 + 16 + seg + 16 + 16) rounded up to 16. With v != NEB_RELAY_NONE, after t's key check and
+ * before segment-time validation: v >= ntunnels or tunnel v without a usable key of this algorithm
+ * -> packet_status NEB_STATUS_BAD_KEY (no relay found: the reference returns before
+ * SegmentSuperpacket, inside.go:195-198); v == t or via[v].tunnel != NEB_RELAY_NONE (a relay is
+ * always reached directly: the reference sends to relayHostInfo.GetRemote()) -> NEB_STATUS_INVALID;
+ * either way no wire and no counter on any tunnel.
+ * Segment j of a via read takes the next counter c of tunnel t (inside.go:127); its slot holds at
+ * +16 header.Encode(1, Message, 0, tunnels[t].remote_index, c), at +32 the ciphertext, then the
+ * inner tag: the direct wire of the same counter. c >= NEB_REJECT_AFTER_MESSAGES: wire_status
+ * NEB_STATUS_EXHAUSTED, c still used, no counter of v (sendInsideEncrypt returns nil before
+ * prepareSendVia, inside.go:204-207). Otherwise the segment takes the next counter r of tunnel v
+ * (prepareSendVia, inside.go:442-501); r >= NEB_REJECT_AFTER_MESSAGES: NEB_STATUS_EXHAUSTED, r still
+ * used (neb_relay_forward_batch's rule). Otherwise bytes 0..15 of the slot are
+ * header.Encode(1, Message, MessageRelay, via[t].remote_index, r), the last 16 bytes the tag of the
+ * AD-only seal under v's key with nonce r over slot[0 : 48 + seg], and wires[].len = seg + 64. The
+ * bytes of a dropped slot are unspecified. wires[].counter is the inner counter c; wires[].reserved
+ * is NEB_TX_WIRE_VIA for a via wire (send it to the relay's remote) and 0 for a direct one. Direct
+ * reads of the batch behave as in neb_tx_seal_batch.
+ * Counters: tunnel v hands out message_counter + 1, + 2, ... in batch order (packet, then segment)
+ * to its own direct segments and to the outer headers of the via segments routed through it whose
+ * inner counter was not exhausted. tunnels[].message_counter advances on the device by the
+ * counters taken, so a via batch, neb_tx_seal_batch and neb_relay_forward_batch on one tunnel array
+ * and stream share the counters without gaps or repeats.
+ * key_hint applies to the inner seal (the targets' keys). The outer AD-only seal is a second pass
+ * on the same stream; it runs as a single-key batch when every relay tunnel named in via has the
+ * same key. The device form reads that one word back while the batch runs (it waits for the work
+ * queued on `stream` before this call, not for the batch). A via wire whose relay key is destroyed
+ * while the batch runs may get the outer seal's NEB_STATUS_BAD_KEY. */
+NEB_API int neb_tx_seal_via_batch(neb_engine* e, int alg, neb_tx_tunnel* d_tunnels, uint32_t ntunnels,
+                                  const neb_relay_route* d_via, const neb_tx_packet* d_packets, uint32_t npackets,
+                                  const uint8_t* d_in, uint8_t* d_out, size_t out_cap, neb_tx_wire* d_wires,
+                                  int32_t* d_wire_status, uint32_t max_wires, uint32_t* d_nwires,
+                                  int32_t* d_packet_status, uint32_t key_hint, void* stream);
+/* The same over host memory (synchronous); via is uploaded beside the tunnels. */
+NEB_API int neb_tx_seal_via_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnels, uint32_t ntunnels,
+                                       const neb_relay_route* via, const neb_tx_packet* packets, uint32_t npackets,
+                                       const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap,
+                                       neb_tx_wire* wires, int32_t* wire_status, uint32_t max_wires,
+                                       uint32_t* nwires, int32_t* packet_status, uint32_t key_hint);
 /* ---- receive: opened packets -> TUN writes (TSO / USO superpackets) ---------------------------- */
 /* What the reference does between the open and the TUN write: MultiCoalescer.Commit per packet, then
  * Flush (overlay/batch/multi_coalesce.go): sort by (epoch, counter), coalesce in-flow TCP / UDP runs

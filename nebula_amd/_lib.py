@@ -47,7 +47,8 @@ KEYS_MIXED = 0xFFFFFFFF
 KNOB_HOST_MODE, KNOB_SUB_BINS_FROM, KNOB_SINGLE_MAX_GRID, KNOB_RX_STRICT, KNOB_TILE_BINS_FROM = 0, 1, 2, 3, 4
 KNOB_SMALL_BATCH, KNOB_FRONT_GROUPS = 5, 6
 KNOB_COALESCE_HASH_BITS = 7  # the device coalescer's flow hash keeps this many bits (tests: collisions)
-RELAY_NONE = 0xFFFFFFFF  # neb_relay_route.tunnel: do not forward
+RELAY_NONE = 0xFFFFFFFF  # neb_relay_route.tunnel: do not forward (neb_tx_seal_via_batch: sent directly)
+TX_WIRE_VIA = 1  # neb_tx_wire.reserved of a wire sent through a relay (neb_tx_seal_via_batch)
 RX_OWN_SOURCE = 0x80000000  # or-ed into neb_rx_packet.len: outside.go:66-74 refused the datagram
 
 # neb_desc (include/nebula_aead.h)
@@ -128,6 +129,10 @@ SIGNATURES = {
     "neb_tx_seal_batch": (_i, [_vp, _i, _vp, _u32, _vp, _u32, _vp, _vp, _sz, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "neb_tx_seal_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _vp, _vp,
                                     _u32]),
+    "neb_tx_seal_via_batch": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _sz, _vp, _vp, _u32, _vp, _vp, _u32,
+                                   _vp]),
+    "neb_tx_seal_via_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _vp,
+                                        _vp, _u32]),
     "neb_rx_open_wire_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_rx_open_wire_batch": (_i, [_vp, _i, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "neb_relay_forward_batch": (_i, [_vp, _i, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),

@@ -198,6 +198,9 @@ struct TxSpace {
     StreamTag last;  // the stream `done` was last recorded on
     uint8_t* d_io = nullptr;  // neb_tx_seal_batch_host staging
     size_t io_cap = 0;
+    // through a relay (neb_tx_seal_via_batch): the relay tunnels' one key, read back for the outer seal
+    uint32_t* h_via_key = nullptr;  // pinned
+    hipEvent_t via_ev = nullptr;
     std::mutex mu;
 };
 
@@ -632,6 +635,8 @@ NEB_API int neb_engine_destroy(neb_engine* e) {
     if (e->tx.done) { hipEventSynchronize(e->tx.done); hipEventDestroy(e->tx.done); }
     if (e->tx.mem) hipFree(e->tx.mem);
     if (e->tx.d_io) hipFree(e->tx.d_io);
+    if (e->tx.h_via_key) hipHostFree(e->tx.h_via_key);
+    if (e->tx.via_ev) hipEventDestroy(e->tx.via_ev);
     if (e->co.done) { hipEventSynchronize(e->co.done); hipEventDestroy(e->co.done); }
     if (e->co.mem) hipFree(e->co.mem);
     for (auto& r : e->rx.slot) {
@@ -1829,33 +1834,51 @@ static hipError_t tx_reserve(neb_engine* e, uint32_t n, uint32_t ntun, uint32_t 
 }
 
 // caller holds e->tx.mu
-static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, const neb_tx_packet* d_pk, uint32_t npk,
-                  const uint8_t* d_in, uint8_t* d_out, size_t out_cap, neb_tx_wire* d_wires, int32_t* d_wire_status,
-                  uint32_t max_wires, uint32_t* d_nwires, int32_t* d_pk_status, uint32_t key_hint, hipStream_t s) {
+// d_via (optional): the tunnels' relays (neb_tx_seal_via_batch)
+static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, const neb_relay_route* d_via,
+                  const neb_tx_packet* d_pk, uint32_t npk, const uint8_t* d_in, uint8_t* d_out, size_t out_cap,
+                  neb_tx_wire* d_wires, int32_t* d_wire_status, uint32_t max_wires, uint32_t* d_nwires,
+                  int32_t* d_pk_status, uint32_t key_hint, hipStream_t s) {
     TxSpace& tx = e->tx;
     HIP_TRY(tx_reserve(e, npk, ntun, max_wires));
     if (!tx.last.same(s)) HIP_TRY(hipStreamWaitEvent(s, tx.done, 0));
-    HIP_TRY(neb_tx_plan(d_pk, npk, d_in, d_tun, ntun, e->d_keys, e->max_keys, alg, &tx.ws, out_cap, max_wires,
+    if (d_via) {
+        // the relay tunnels' one key, for a single-key outer seal: asked for first, read back after
+        // the inner seal is enqueued, so the host waits for this word only while the device works
+        if (!tx.h_via_key) HIP_TRY(hipHostMalloc((void**)&tx.h_via_key, sizeof(uint32_t), hipHostMallocDefault));
+        if (!tx.via_ev) HIP_TRY(hipEventCreateWithFlags(&tx.via_ev, hipEventDisableTiming));
+        HIP_TRY(neb_tx_via_key(d_tun, ntun, d_via, tx.h_via_key, s));
+        HIP_TRY(hipEventRecord(tx.via_ev, s));
+    }
+    HIP_TRY(neb_tx_plan(d_pk, npk, d_in, d_tun, ntun, d_via, e->d_keys, e->max_keys, alg, &tx.ws, out_cap, max_wires,
                         d_pk_status, d_nwires, s));
     // one tunnel key with AES-GCM: the seal sums the payload into the L4 checksums itself, so the
     // segment kernel does not read the payload (aes_gcm.hip gcm_csum_fix)
     const bool cs = neb::kTxSealFromInput && NEB_TX_CSUM_SEAL && alg == NEB_ALG_AESGCM && key_hint != NEB_KEYS_MIXED;
     const uint32_t cs_slots = cs ? neb_gcm_single_slots(max_wires, e->cu_count, 0, 2) : 0u;
-    HIP_TRY(neb_tx_segment(d_pk, npk, d_in, d_tun, d_out, &tx.ws, d_wires, d_nwires, max_wires, e->cu_count, cs_slots,
-                           s));
+    HIP_TRY(neb_tx_segment(d_pk, npk, d_in, d_tun, d_via, d_out, &tx.ws, d_wires, d_nwires, max_wires, e->cu_count,
+                           cs_slots, s));
     HIP_TRY(launch_batch(e, alg, 0, tx.ws.seal_desc, max_wires, d_out, d_wire_status, key_hint, s, d_nwires, nullptr,
                          cs ? 2 : (int)neb::kTxSealFromInput));
     HIP_TRY(neb_tx_finish(d_tun, npk, ntun, &tx.ws, s));
+    if (d_via && max_wires) {
+        // prepareSendVia's tags: the AD-only seal over the compacted via wires, behind the inner seal
+        HIP_TRY(hipEventSynchronize(tx.via_ev));
+        uint32_t hint = *tx.h_via_key;
+        if (hint != NEB_KEYS_MIXED && check_batch(e, alg, hint) != NEB_OK) hint = NEB_KEYS_MIXED;
+        HIP_TRY(launch_batch(e, alg, 0, tx.ws.via_desc, max_wires, d_out, tx.ws.via_status, hint, s, tx.ws.nvia));
+        HIP_TRY(neb_tx_via_fix(&tx.ws, max_wires, d_wire_status, s));
+        note_use(e, hint, s);
+    }
     HIP_TRY(hipEventRecord(tx.done, s));
     tx.last.set(s);
     return NEB_OK;
 }
 
-NEB_API int neb_tx_seal_batch(neb_engine* e, int alg, neb_tx_tunnel* d_tunnels, uint32_t ntunnels,
-                              const neb_tx_packet* d_packets, uint32_t npackets, const uint8_t* d_in,
-                              uint8_t* d_out, size_t out_cap, neb_tx_wire* d_wires, int32_t* d_wire_status,
-                              uint32_t max_wires, uint32_t* d_nwires, int32_t* d_packet_status, uint32_t key_hint,
-                              void* stream) {
+static int tx_device(neb_engine* e, int alg, neb_tx_tunnel* d_tunnels, uint32_t ntunnels, const neb_relay_route* d_via,
+                     const neb_tx_packet* d_packets, uint32_t npackets, const uint8_t* d_in, uint8_t* d_out,
+                     size_t out_cap, neb_tx_wire* d_wires, int32_t* d_wire_status, uint32_t max_wires,
+                     uint32_t* d_nwires, int32_t* d_packet_status, uint32_t key_hint, void* stream) {
     int rc = check_batch(e, alg, key_hint);
     if (rc != NEB_OK) return rc;
     if (!d_nwires || (npackets && (!d_packets || !d_in || !d_packet_status || !d_tunnels)) ||
@@ -1868,16 +1891,34 @@ NEB_API int neb_tx_seal_batch(neb_engine* e, int alg, neb_tx_tunnel* d_tunnels, 
         return NEB_OK;
     }
     std::lock_guard<std::mutex> g(e->tx.mu);
-    rc = tx_run(e, alg, d_tunnels, ntunnels, d_packets, npackets, d_in, d_out, out_cap, d_wires, d_wire_status,
+    rc = tx_run(e, alg, d_tunnels, ntunnels, d_via, d_packets, npackets, d_in, d_out, out_cap, d_wires, d_wire_status,
                 max_wires, d_nwires, d_packet_status, key_hint, s);
     if (rc == NEB_OK) note_use(e, key_hint, s);
     return rc;
 }
 
-NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnels, uint32_t ntunnels,
-                                   const neb_tx_packet* packets, uint32_t npackets, const uint8_t* in, size_t in_len,
-                                   uint8_t* out, size_t out_cap, neb_tx_wire* wires, int32_t* wire_status,
-                                   uint32_t max_wires, uint32_t* nwires, int32_t* packet_status, uint32_t key_hint) {
+NEB_API int neb_tx_seal_batch(neb_engine* e, int alg, neb_tx_tunnel* d_tunnels, uint32_t ntunnels,
+                              const neb_tx_packet* d_packets, uint32_t npackets, const uint8_t* d_in,
+                              uint8_t* d_out, size_t out_cap, neb_tx_wire* d_wires, int32_t* d_wire_status,
+                              uint32_t max_wires, uint32_t* d_nwires, int32_t* d_packet_status, uint32_t key_hint,
+                              void* stream) {
+    return tx_device(e, alg, d_tunnels, ntunnels, nullptr, d_packets, npackets, d_in, d_out, out_cap, d_wires,
+                     d_wire_status, max_wires, d_nwires, d_packet_status, key_hint, stream);
+}
+
+NEB_API int neb_tx_seal_via_batch(neb_engine* e, int alg, neb_tx_tunnel* d_tunnels, uint32_t ntunnels,
+                                  const neb_relay_route* d_via, const neb_tx_packet* d_packets, uint32_t npackets,
+                                  const uint8_t* d_in, uint8_t* d_out, size_t out_cap, neb_tx_wire* d_wires,
+                                  int32_t* d_wire_status, uint32_t max_wires, uint32_t* d_nwires,
+                                  int32_t* d_packet_status, uint32_t key_hint, void* stream) {
+    return tx_device(e, alg, d_tunnels, ntunnels, ntunnels ? d_via : nullptr, d_packets, npackets, d_in, d_out, out_cap,
+                     d_wires, d_wire_status, max_wires, d_nwires, d_packet_status, key_hint, stream);
+}
+
+static int tx_host(neb_engine* e, int alg, neb_tx_tunnel* tunnels, uint32_t ntunnels, const neb_relay_route* via,
+                   const neb_tx_packet* packets, uint32_t npackets, const uint8_t* in, size_t in_len, uint8_t* out,
+                   size_t out_cap, neb_tx_wire* wires, int32_t* wire_status, uint32_t max_wires, uint32_t* nwires,
+                   int32_t* packet_status, uint32_t key_hint) {
     int rc = check_batch(e, alg, key_hint);
     if (rc != NEB_OK) return rc;
     if (!nwires || (npackets && (!packets || !in || !packet_status || (ntunnels && !tunnels))) ||
@@ -1901,7 +1942,8 @@ NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnel
     const size_t o_ws = o_w + align_up((size_t)max_wires * sizeof(neb_tx_wire), 256);
     const size_t o_ps = o_ws + align_up((size_t)max_wires * 4, 256);
     const size_t o_n = o_ps + align_up((size_t)npackets * 4, 256);
-    const size_t total = o_n + 256;
+    const size_t o_via = o_n + 256;
+    const size_t total = o_via + (via ? align_up((size_t)ntunnels * sizeof(neb_relay_route), 256) : 0);
     std::vector<neb_tx_packet> rebased(packets, packets + npackets);
     for (auto& p : rebased) p.in_off -= lo;
     std::lock_guard<std::mutex> g(e->tx.mu);
@@ -1927,8 +1969,10 @@ NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnel
     if (ntunnels) HIP_TRY(hipMemcpyAsync(d_tun, tunnels, ntunnels * sizeof(neb_tx_tunnel), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_pk, rebased.data(), npackets * sizeof(neb_tx_packet), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_in, in + lo, span, hipMemcpyHostToDevice, s));
-    rc = tx_run(e, alg, d_tun, ntunnels, d_pk, npackets, d + o_in, d + o_out, out_cap, d_wires, d_wst, max_wires, d_n,
-                d_pst, key_hint, s);
+    auto* d_via = via ? (neb_relay_route*)(d + o_via) : nullptr;
+    if (via) HIP_TRY(hipMemcpyAsync(d_via, via, ntunnels * sizeof(neb_relay_route), hipMemcpyHostToDevice, s));
+    rc = tx_run(e, alg, d_tun, ntunnels, d_via, d_pk, npackets, d + o_in, d + o_out, out_cap, d_wires, d_wst, max_wires,
+                d_n, d_pst, key_hint, s);
     if (rc != NEB_OK) return rc;
     unsigned long long tot[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(tot, tx.ws.totals, sizeof tot, hipMemcpyDeviceToHost, s));
@@ -1944,6 +1988,23 @@ NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnel
     }
     *nwires = nw;
     return NEB_OK;
+}
+
+NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnels, uint32_t ntunnels,
+                                   const neb_tx_packet* packets, uint32_t npackets, const uint8_t* in, size_t in_len,
+                                   uint8_t* out, size_t out_cap, neb_tx_wire* wires, int32_t* wire_status,
+                                   uint32_t max_wires, uint32_t* nwires, int32_t* packet_status, uint32_t key_hint) {
+    return tx_host(e, alg, tunnels, ntunnels, nullptr, packets, npackets, in, in_len, out, out_cap, wires, wire_status,
+                   max_wires, nwires, packet_status, key_hint);
+}
+
+NEB_API int neb_tx_seal_via_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnels, uint32_t ntunnels,
+                                       const neb_relay_route* via, const neb_tx_packet* packets, uint32_t npackets,
+                                       const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap,
+                                       neb_tx_wire* wires, int32_t* wire_status, uint32_t max_wires,
+                                       uint32_t* nwires, int32_t* packet_status, uint32_t key_hint) {
+    return tx_host(e, alg, tunnels, ntunnels, ntunnels ? via : nullptr, packets, npackets, in, in_len, out, out_cap,
+                   wires, wire_status, max_wires, nwires, packet_status, key_hint);
 }
 
 // ---- receive coalescer (coalesce.hip) -----------------------------------------------------------

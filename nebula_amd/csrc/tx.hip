@@ -19,6 +19,15 @@
 //   seal               the AES-GCM / ChaCha20-Poly1305 batch kernels, in place, with the segment
 //                      count read on the device.
 //   tx_finish_kernel   tunnels' message counters advance by their segments in this batch.
+//
+// Through a relay (neb_tx_seal_via_batch, inside.go:178-223 + prepareSendVia :442-501): a read whose
+// tunnel t has via[t].tunnel = v is sealed under t's key 16 bytes further into a slot 32 bytes
+// larger, behind a Message/Relay header with v's next counter, and a second, AD-only seal under v's
+// key puts its tag behind the inner one. The plan assigns counters on two levels: a tunnel with a via
+// is never a relay, so its counters depend on its own reads alone (the first assignment); a read
+// with first inner counter c0 and s segments takes min(s, RejectAfter - 1 - c0) outer counters, and
+// the direct tunnels' counters follow from a second assignment over their direct segments and
+// those counts. The outer seals are compacted (ws.via_desc, ws.nvia) for the existing seal kernels.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
@@ -60,12 +69,27 @@ struct TxParsed {
     TxPlan plan;
     int32_t st;
     uint64_t scan;  // nseg << 40 | output bytes
+    uint32_t via_tun;  // the relay tunnel of a read that is sent through one, else NEB_RELAY_NONE
 };
+
+__device__ __forceinline__ bool tx_key_ok(uint32_t key, const uint32_t* __restrict__ keys, uint32_t max_keys, int alg) {
+    return key < max_keys && keys[(size_t)key * kKeyRecDwords + kRecAlg] == (uint32_t)alg;
+}
+// the outer counters a via read takes: its segments whose inner counter c0 + 1 .. c0 + nseg is not
+// exhausted (sendInsideEncrypt returns nil before prepareSendVia, inside.go:204-207); the same form
+// gives the outer seals of a read whose first outer counter follows r0
+__device__ __forceinline__ uint32_t tx_live_counters(uint64_t c0, uint32_t nseg) {
+    if (c0 >= kRejectAfterMessages - 1u) return 0u;
+    const uint64_t room = kRejectAfterMessages - 1u - c0;
+    return room < nseg ? (uint32_t)room : nseg;
+}
 
 __device__ TxParsed tx_parse_one(const neb_tx_packet& P, const uint8_t* __restrict__ in,
                                  const neb_tx_tunnel* __restrict__ tun, uint32_t ntun,
-                                 const uint32_t* __restrict__ keys, uint32_t max_keys, int alg) {
+                                 const neb_relay_route* __restrict__ via, const uint32_t* __restrict__ keys,
+                                 uint32_t max_keys, int alg) {
     TxPlan plan{};
+    uint32_t v = NEB_RELAY_NONE;
     int32_t st = NEB_STATUS_OK;
     const uint8_t* b = in + P.in_off;
     const uint32_t len = P.len, cs = P.csum_start, co = P.csum_offset, gso = P.gso_size;
@@ -113,12 +137,22 @@ __device__ TxParsed tx_parse_one(const neb_tx_packet& P, const uint8_t* __restri
             if (key >= max_keys || keys[(size_t)key * kKeyRecDwords + kRecAlg] != (uint32_t)alg) st = NEB_STATUS_BAD_KEY;
         }
     }
+    // 2b. the tunnel is reached through a relay: none usable returns before SegmentSuperpacket
+    // (inside.go:195-198); a relay is itself always reached directly
+    if (st == NEB_STATUS_OK && via) {
+        v = via[P.tunnel].tunnel;
+        if (v != NEB_RELAY_NONE) {
+            if (v >= ntun || !tx_key_ok(tun[v].key_id, keys, max_keys, alg)) st = NEB_STATUS_BAD_KEY;
+            else if (v == P.tunnel || via[v].tunnel != NEB_RELAY_NONE) st = NEB_STATUS_INVALID;
+        }
+    }
+    const uint32_t vx = v != NEB_RELAY_NONE ? 32u : 0u;  // the outer header and tag
     // 3. segment time: SegmentTCP/UDP's early errors and baseIPv4HdrSum's IHL bound
     if (st == NEB_STATUS_OK) {
         if (plan.kind == kTxPass || plan.kind == kTxFinish) {
             plan.nseg = 1;
             plan.hdr_len = 0;
-            plan.full_slot = align16(len + 32u);
+            plan.full_slot = align16(len + 32u) + vx;
         } else {
             const bool v4 = ver == 4u;
             if (cs == 0u || hl > kTxMaxHdr) st = NEB_STATUS_INVALID;
@@ -131,7 +165,7 @@ __device__ TxParsed tx_parse_one(const neb_tx_packet& P, const uint8_t* __restri
                 plan.nseg = pay ? (pay + gso - 1u) / gso : 1u;
                 plan.hdr_len = hl;
                 plan.v4 = v4;
-                plan.full_slot = align16(hl + gso + 32u);
+                plan.full_slot = align16(hl + gso + 32u) + vx;
                 // the constants of every segment header, from the pristine superpacket header
                 const uint32_t pseudo = (v4 ? csum_range(b, 12, 20) : csum_range(b, 8, 40)) +
                                         (plan.kind == kTxTcp ? 6u : 17u);  // basePseudoSum
@@ -163,21 +197,25 @@ __device__ TxParsed tx_parse_one(const neb_tx_packet& P, const uint8_t* __restri
         } else {
             const uint32_t pay = len - plan.hdr_len;
             const uint32_t last = pay - (plan.nseg - 1u) * gso;
-            bytes = (uint64_t)(plan.nseg - 1u) * plan.full_slot + align16(plan.hdr_len + last + 32u);
+            bytes = (uint64_t)(plan.nseg - 1u) * plan.full_slot + align16(plan.hdr_len + last + 32u) + vx;
         }
+        plan.via = vx != 0u;
     } else {
         plan.nseg = 0;
+        v = NEB_RELAY_NONE;
     }
-    return TxParsed{plan, st, ((uint64_t)plan.nseg << 40) | bytes};
+    return TxParsed{plan, st, ((uint64_t)plan.nseg << 40) | bytes, v};
 }
 
 __global__ void tx_parse_kernel(const neb_tx_packet* __restrict__ pk, uint32_t n, const uint8_t* __restrict__ in,
-                                const neb_tx_tunnel* __restrict__ tun, uint32_t ntun, const uint32_t* __restrict__ keys,
+                                const neb_tx_tunnel* __restrict__ tun, uint32_t ntun,
+                                const neb_relay_route* __restrict__ via, const uint32_t* __restrict__ keys,
                                 uint32_t max_keys, int alg, TxWs ws, int32_t* __restrict__ pk_status) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const neb_tx_packet P = pk[i];
-    const TxParsed r = tx_parse_one(P, in, tun, ntun, keys, max_keys, alg);
+    const TxParsed r = tx_parse_one(P, in, tun, ntun, via, keys, max_keys, alg);
+    if (via) ws.via_tun[i] = r.via_tun;
     ws.plan[i] = r.plan;
     ws.scan_in[i] = r.scan;
     ws.tun_key[i] = r.st == NEB_STATUS_OK ? P.tunnel : ntun;
@@ -195,25 +233,82 @@ __global__ void tx_segmap_kernel(uint32_t n, uint32_t max_wires, uint64_t out_ca
     for (uint32_t k = (uint32_t)(pre >> 40) + (threadIdx.x & 63u); k < (uint32_t)end_seg; k += 64u) ws.seg_pkt[k] = p;
 }
 
+// LEVEL2 (through a relay, the second assignment): a via read counts its outer counters
+template <bool LEVEL2>
 __global__ void tx_gather_kernel(uint32_t n, TxWs ws) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) ws.nseg_sorted[i] = ws.plan[ws.idx_sorted[i]].nseg;
+    if (i >= n) return;
+    const uint32_t p = ws.idx_sorted[i], nseg = ws.plan[p].nseg;
+    if constexpr (LEVEL2) {
+        ws.nseg_sorted[i] = ws.via_tun[p] != NEB_RELAY_NONE ? tx_live_counters(ws.ctr_base[p], nseg) : nseg;
+    } else {
+        ws.nseg_sorted[i] = nseg;
+    }
+}
+
+// Through a relay, between the two assignments: a via read is keyed by its relay tunnel for the
+// second one (every other read keeps its key: its tunnel, or ntun when it was dropped).
+__global__ void tx_via_rekey_kernel(uint32_t n, TxWs ws) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) ws.nvia[0] = 0;
+    if (i >= n) return;
+    const uint32_t v = ws.via_tun[i];
+    if (v != NEB_RELAY_NONE) ws.tun_key[i] = v;
 }
 
 // Counter offsets back in batch order; the fitting prefix; per-tunnel totals; the batch totals.
+// LEVEL2 (through a relay): the second assignment, over the direct tunnels' own segments and the
+// outer counters of the via reads routed through them. It rewrites the direct reads' bases and the
+// direct tunnels' totals (the first assignment did not count the outer counters); a via read gets
+// its outer base and the compacted place of its outer seals, by one atomic per wave (the seal's
+// results do not depend on the order of its batch).
+template <bool LEVEL2>
 __global__ void tx_scatter_kernel(uint32_t n, const neb_tx_tunnel* __restrict__ tun, uint32_t ntun, uint64_t out_cap,
                                   uint32_t max_wires, TxWs ws, int32_t* __restrict__ pk_status,
                                   uint32_t* __restrict__ d_nwires) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t p = ws.idx_sorted[i];
-    const uint64_t pre = ws.scan_out[p], own = ws.scan_in[p];
+    if (!LEVEL2 && i >= n) return;  // (LEVEL2: whole waves reach its shuffles)
+    const uint32_t p = i < n ? ws.idx_sorted[i] : 0u;
+    uint64_t pre = 0, own = 0;
+    if (i < n) {
+        pre = ws.scan_out[p];
+        own = ws.scan_in[p];
+    }
     const uint64_t end_seg = (pre >> 40) + (own >> 40);
     const uint64_t end_bytes = (pre & kTxBytesMask) + (own & kTxBytesMask);
-    const uint32_t t = ws.tun_key_sorted[i];
-    // tx_finish_kernel advances the counters only after the segment kernel has run
-    ws.ctr_base[p] = (t < ntun ? tun[t].message_counter : 0ull) + ws.ctr_sorted[i];
+    const uint32_t t = i < n ? ws.tun_key_sorted[i] : ntun;
     const bool fits = end_seg <= max_wires && end_bytes <= out_cap;
+    // tx_finish_kernel advances the counters only after the segment kernel has run
+    const uint64_t base = (t < ntun ? tun[t].message_counter : 0ull) + (i < n ? ws.ctr_sorted[i] : 0u);
+    uint32_t taken = (uint32_t)(own >> 40);  // counters this read takes of tunnel t
+    if constexpr (LEVEL2) {
+        const bool is_via = i < n && ws.via_tun[p] != NEB_RELAY_NONE;
+        uint32_t nd = 0;
+        if (is_via) {
+            taken = ws.nseg_sorted[i];
+            ws.via_ctr_base[p] = base;
+            if (t < ntun && fits) nd = tx_live_counters(base, taken);
+        } else if (i < n) {
+            ws.ctr_base[p] = base;
+        }
+        // every lane of the wave is here: compacted places for this wave's outer seals
+        uint32_t incl = nd;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
+            if ((threadIdx.x & 63u) >= (uint32_t)o) incl += up;
+        }
+        const uint32_t wave_total = (uint32_t)__shfl((int)incl, 63);
+        uint32_t wave_base = 0;
+        if (wave_total) {
+            if ((threadIdx.x & 63u) == 63u) wave_base = atomicAdd(&ws.nvia[0], wave_total);
+            wave_base = (uint32_t)__shfl((int)wave_base, 63);
+        }
+        if (is_via) ws.via_pos[p] = wave_base + incl - nd;
+        if (i >= n) return;
+    } else {
+        ws.ctr_base[p] = base;
+    }
     if (t < ntun) {
         if (fits) {
             // the last fitting packet of its tunnel's run (sorted by tunnel, then batch order) writes
@@ -224,7 +319,7 @@ __global__ void tx_scatter_kernel(uint32_t n, const neb_tx_tunnel* __restrict__ 
                 const uint64_t e = ws.scan_out[q] + ws.scan_in[q];
                 last = !((e >> 40) <= max_wires && (e & kTxBytesMask) <= out_cap);
             }
-            if (last) ws.tun_total[t] = ws.ctr_sorted[i] + (own >> 40);
+            if (last) ws.tun_total[t] = ws.ctr_sorted[i] + taken;
         } else {
             pk_status[p] = NEB_STATUS_NO_SPACE;  // outside the fitting prefix
         }
@@ -277,10 +372,14 @@ struct TxSegOp {
     }
 };
 
-template <uint32_t IT, bool PARSED>
+// VIA (through a relay): the two-level assignment. The first sort keys only the via reads, by their
+// own tunnel, and leaves each one's outer counters in s_end; the second keys every read by the
+// tunnel whose counters it takes next (a via read: its relay), with those counts as its weight.
+// The two levels touch disjoint tunnels, so each stores its counters after its own barrier.
+template <uint32_t IT, bool PARSED, bool VIA>
 __global__ __launch_bounds__(kTxPlanThreads) void tx_plan_small_kernel(
     const neb_tx_packet* __restrict__ pk, uint32_t n, const uint8_t* __restrict__ in, neb_tx_tunnel* __restrict__ tun,
-    uint32_t ntun, const uint32_t* __restrict__ keys, uint32_t max_keys, int alg, uint64_t out_cap, uint32_t max_wires,
+    uint32_t ntun, const neb_relay_route* __restrict__ via, const uint32_t* __restrict__ keys, uint32_t max_keys, int alg, uint64_t out_cap, uint32_t max_wires,
     int key_bits, TxWs ws, int32_t* __restrict__ pk_status, uint32_t* __restrict__ d_nwires) {
     static_assert(IT <= kTxPlanItems, "the LDS arrays hold kTxPlanSmallMax reads");
     using Sort = hipcub::BlockRadixSort<uint32_t, kTxPlanThreads, IT, uint32_t>;
@@ -313,8 +412,9 @@ __global__ __launch_bounds__(kTxPlanThreads) void tx_plan_small_kernel(
             s_key[i] = ws.tun_key[i];
         } else {
             const neb_tx_packet P = pk[i];
-            const TxParsed r = tx_parse_one(P, in, tun, ntun, keys, max_keys, alg);
+            const TxParsed r = tx_parse_one(P, in, tun, ntun, via, keys, max_keys, alg);
             ws.plan[i] = r.plan;
+            if constexpr (VIA) ws.via_tun[i] = r.via_tun;
             pk_status[i] = r.st;
             s_nseg[i] = r.plan.nseg;
             s_end[i] = (uint32_t)(r.scan & kTxBytesMask);
@@ -334,6 +434,19 @@ __global__ __launch_bounds__(kTxPlanThreads) void tx_plan_small_kernel(
         }
     }
     __syncthreads();
+    uint32_t vt[VIA ? IT : 1];  // each read's relay tunnel
+    (void)vt;
+    if constexpr (VIA) {
+#pragma unroll
+        for (uint32_t k = 0; k < IT; k++) {
+            const uint32_t i = t * IT + k;
+            vt[k] = NEB_RELAY_NONE;
+            if (i < n) {
+                vt[k] = ws.via_tun[i];
+                s_end[i] = s_nseg[i];  // the second level's weight of a direct read
+            }
+        }
+    }
     TXPROF(T1);
     // 2. batch-order exclusive prefix of (segments, bytes); the fitting prefix
     uint64_t tot = 0;
@@ -369,44 +482,85 @@ __global__ __launch_bounds__(kTxPlanThreads) void tx_plan_small_kernel(
     }
     TXPROF(T2);
     // 3. counters: a stable sort by tunnel keeps batch order inside each tunnel's run
-    __syncthreads();
-    Sort(tmp.sort).Sort(key, idx, 0, key_bits);
+    constexpr uint32_t kIdxMask = VIA ? 0x7FFFFFFFu : 0xFFFFFFFFu;  // VIA: bit 31 of idx = a via read
+    // one assignment: out(read, via flag, its tunnel's counter before its first one, its weight)
+    auto assign = [&](uint32_t(&key)[IT], uint32_t(&idx)[IT], const uint32_t* s_val, auto&& out) {
+        __syncthreads();
+        Sort(tmp.sort).Sort(key, idx, 0, key_bits);
 #pragma unroll
-    for (uint32_t k = 0; k < IT; k++) s_key[t * IT + k] = key[k];
-    __syncthreads();
-    uint32_t val[IT], head[IT];
-    TxSegPair agg{0u, 0u};
+        for (uint32_t k = 0; k < IT; k++) s_key[t * IT + k] = key[k];
+        __syncthreads();
+        uint32_t val[IT], head[IT];
+        TxSegPair agg{0u, 0u};
 #pragma unroll
-    for (uint32_t k = 0; k < IT; k++) {
-        const uint32_t r = t * IT + k;
-        val[k] = key[k] < ntun ? s_nseg[idx[k]] : 0u;
-        head[k] = r == 0u || s_key[r - 1u] != key[k];
-        agg = TxSegOp{}(agg, TxSegPair{head[k], val[k]});
+        for (uint32_t k = 0; k < IT; k++) {
+            const uint32_t r = t * IT + k;
+            val[k] = key[k] < ntun ? s_val[idx[k] & kIdxMask] : 0u;
+            head[k] = r == 0u || s_key[r - 1u] != key[k];
+            agg = TxSegOp{}(agg, TxSegPair{head[k], val[k]});
+        }
+        TxSegPair carry;
+        ScanSeg(tmp.seg).ExclusiveScan(agg, carry, TxSegPair{0u, 0u}, TxSegOp{});
+        uint32_t run = carry.sum;
+        uint64_t newctr[IT];
+        bool last[IT];
+#pragma unroll
+        for (uint32_t k = 0; k < IT; k++) {
+            const uint32_t r = t * IT + k;
+            if (head[k]) run = 0;
+            last[k] = false;
+            if (key[k] < ntun) {
+                const uint64_t base = tun[key[k]].message_counter;
+                out(idx[k] & kIdxMask, (idx[k] & ~kIdxMask) != 0u, base + run, val[k]);
+                last[k] = r + 1u == kTxPlanThreads * IT || s_key[r + 1u] != key[k];
+                newctr[k] = base + run + val[k];
+            }
+            run += val[k];
+        }
+        __syncthreads();  // every read of the old counters is done
+#pragma unroll
+        for (uint32_t k = 0; k < IT; k++)
+            if (last[k]) tun[key[k]].message_counter = newctr[k];
+    };
+    if constexpr (!VIA) {
+        assign(key, idx, s_nseg, [&](uint32_t i, bool, uint64_t c0, uint32_t) { ws.ctr_base[i] = c0; });
+    } else {
+        uint32_t key2[IT], idx2[IT];
+#pragma unroll
+        for (uint32_t k = 0; k < IT; k++) {
+            const bool is_via = key[k] < ntun && vt[k] != NEB_RELAY_NONE;
+            key2[k] = is_via ? vt[k] : key[k];
+            idx2[k] = idx[k] | (is_via ? ~kIdxMask : 0u);
+            if (!is_via) key[k] = ntun;
+        }
+        assign(key, idx, s_nseg, [&](uint32_t i, bool, uint64_t c0, uint32_t nseg) {
+            ws.ctr_base[i] = c0;
+            s_end[i] = tx_live_counters(c0, nseg);
+        });
+        uint32_t nd = 0;  // this thread's outer seals, then their compacted places
+        assign(key2, idx2, s_end, [&](uint32_t i, bool is_via, uint64_t c0, uint32_t cnt) {
+            if (is_via) {
+                ws.via_ctr_base[i] = c0;
+                nd += tx_live_counters(c0, cnt);
+            } else {
+                ws.ctr_base[i] = c0;
+            }
+        });
+        __syncthreads();
+        uint64_t pos, total;
+        Scan64(tmp.scan).ExclusiveSum((uint64_t)nd, pos, total);
+#pragma unroll
+        for (uint32_t k = 0; k < IT; k++) {
+            const uint32_t i = idx2[k] & kIdxMask;
+            if (key2[k] < ntun && (idx2[k] & ~kIdxMask)) {
+                ws.via_pos[i] = (uint32_t)pos;
+                pos += tx_live_counters(ws.via_ctr_base[i], s_end[i]);
+            }
+        }
+        if (t == 0) ws.nvia[0] = (uint32_t)total;
     }
     TXPROF(T3);
-    TxSegPair carry;
-    ScanSeg(tmp.seg).ExclusiveScan(agg, carry, TxSegPair{0u, 0u}, TxSegOp{});
-    uint32_t run = carry.sum;
-    uint64_t newctr[IT];
-    bool last[IT];
-#pragma unroll
-    for (uint32_t k = 0; k < IT; k++) {
-        const uint32_t r = t * IT + k;
-        if (head[k]) run = 0;
-        last[k] = false;
-        if (key[k] < ntun) {
-            const uint64_t base = tun[key[k]].message_counter;
-            ws.ctr_base[idx[k]] = base + run;
-            last[k] = r + 1u == kTxPlanThreads * IT || s_key[r + 1u] != key[k];
-            newctr[k] = base + run + val[k];
-        }
-        run += val[k];
-    }
     TXPROF(T4);
-    __syncthreads();  // every read of the old counters is done
-#pragma unroll
-    for (uint32_t k = 0; k < IT; k++)
-        if (last[k]) tun[key[k]].message_counter = newctr[k];
     TXPROF(T5);
     TXPROF(T6);
 #ifdef NEB_TX_PLAN_PROF
@@ -500,10 +654,14 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
 #ifndef NEB_TX_CSM_BLOCKS
 #define NEB_TX_CSM_BLOCKS 5
 #endif
-template <bool CSM>
+// VIA (through a relay): a via read's image starts 16 bytes further into its slot, behind the
+// Message/Relay header with the relay tunnel's counter, and leaves a second, AD-only descriptor
+// (as relay.hpp neb_relay_send_via's) at its compacted place for the outer seal.
+template <bool CSM, bool VIA>
 __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MINBLOCKS) void tx_segment_kernel(const neb_tx_packet* __restrict__ pk,
                                                                      const uint8_t* __restrict__ in,
                                                                      const neb_tx_tunnel* __restrict__ tun,
+                                                                     const neb_relay_route* __restrict__ via,
                                                                      uint8_t* __restrict__ out, TxWs ws,
                                                                      neb_tx_wire* __restrict__ wires,
                                                                      const uint32_t* __restrict__ d_nwires,
@@ -543,8 +701,15 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
         const uint32_t a = gsok ? j * P.gso_size : 0u;
         const uint32_t pl = !live ? 0u : gsok ? min((uint32_t)P.gso_size, P.len - hl - a) : P.len;
         const uint32_t seg_len = hl + pl;
-        uint8_t* dst = out + slot;
-        const bool work = live && counter < kRejectAfterMessages;  // an exhausted one keeps only its header
+        // through a relay: the inner wire starts vo bytes into the slot; the outer counter r of a
+        // segment whose inner one is not exhausted (exhausted ones are the read's last)
+        const uint32_t vo = VIA && plan.via ? 16u : 0u;
+        uint64_t rctr = 0;
+        if (VIA && vo && live) rctr = ws.via_ctr_base[p] + j + 1u;
+        const bool outer_dead = VIA && vo && rctr >= kRejectAfterMessages;
+        uint8_t* dst = out + slot + vo;
+        // an exhausted one keeps only its header
+        const bool work = live && counter < kRejectAfterMessages && !outer_dead;
         // the seal's checksum: the field inside one 16-B block and inside the prefix the seal reads
         // from the slot, the payload words paired like the checksum start's, e < 1024
         const uint32_t fld = gsok ? (plan.kind == kTxTcp ? cs + 16u : cs + 6u) : cs + co;
@@ -553,16 +718,30 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
                              ((hdr_b - cs) & 1u) == 0u && fld + 2u <= hdr_b && seg_len < 16384u;
 
         if (live && g == 0) {
-            wires[s] = neb_tx_wire{slot, counter, seg_len + 32u, p, j, 0u};
+            wires[s] = neb_tx_wire{slot, counter, seg_len + 32u + 2u * vo, p, j, vo ? (uint32_t)NEB_TX_WIRE_VIA : 0u};
+            // an exhausted outer counter drops the wire: the inner seal reports it from this counter
+            const uint64_t seal_ctr = outer_dead ? rctr : counter;
+            const uint64_t islot = slot + vo;
             if constexpr (kTxSealFromInput) {
                 // plaintext byte x of the segment image: x < hdr from the slot (the patched header, or
                 // a plain packet up to its finished checksum), else the TUN read's byte in_off + a + x
                 const uint32_t kind = (plan.kind == kTxUdp || (plan.kind == kTxFinish && co == 6u)) ? 2u : 1u;
                 const uint32_t fl = seal_cs ? hdr_b | fld << 12 | kind << 24 | (cs & 1u) << 26 : hdr_b;
                 const uint64_t src = (uint64_t)((uintptr_t)(in + P.in_off + a) - (uintptr_t)out);
-                ws.seal_desc[s] = neb_desc{src, slot + 16u, slot, counter, seg_len, 16u, T.key_id, fl};
+                ws.seal_desc[s] = neb_desc{src, islot + 16u, islot, seal_ctr, seg_len, 16u, T.key_id, fl};
             } else {
-                ws.seal_desc[s] = neb_desc{slot + 16u, slot + 16u, slot, counter, seg_len, 16u, T.key_id, 0u};
+                ws.seal_desc[s] = neb_desc{islot + 16u, islot + 16u, islot, seal_ctr, seg_len, 16u, T.key_id, 0u};
+            }
+            if (VIA && vo && work) {
+                // prepareSendVia (inside.go:442-501): header.Encode(1, Message, MessageRelay,
+                // relay.RemoteIndex, r), and the tag over everything before it
+                const neb_relay_route R = via[P.tunnel];
+                const uint32_t at = ws.via_pos[p] + j;
+                ws.via_desc[at] = neb_desc{slot + 48u + seg_len, slot + 48u + seg_len, slot, rctr, 0u, 48u + seg_len,
+                                           tun[R.tunnel].key_id, 0u};
+                ws.via_map[at] = s;
+                store_block(out + slot, make_uint4(0x00000111u, bswap32(R.remote_index), bswap32((uint32_t)(rctr >> 32)),
+                                                   bswap32((uint32_t)rctr)), 16u);
             }
             // header.Encode(Version 1, Message 1, subtype 0, remote index, counter)
             // store_block: `out` may start at any byte address
@@ -767,6 +946,44 @@ __global__ void tx_finish_kernel(neb_tx_tunnel* __restrict__ tun, uint32_t ntun,
     if (t < ntun) tun[t].message_counter += ws.tun_total[t];
 }
 
+// The one key of the relay tunnels `via` names (NEB_KEYS_MIXED: several keys, or no relay): the
+// outer seal then runs as a single-key batch. One workgroup; the word goes straight to the host's
+// pinned memory (no copy on the stream between this kernel and the plan).
+__global__ __launch_bounds__(1024) void tx_via_key_kernel(const neb_tx_tunnel* __restrict__ tun, uint32_t ntun,
+                                                          const neb_relay_route* __restrict__ via,
+                                                          uint32_t* __restrict__ h_key) {
+    __shared__ uint32_t s_lo, s_hi;
+    if (threadIdx.x == 0) {
+        s_lo = 0xFFFFFFFFu;
+        s_hi = 0u;
+    }
+    __syncthreads();
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    bool any = false;
+    for (uint32_t t = threadIdx.x; t < ntun; t += 1024u) {
+        const uint32_t v = via[t].tunnel;
+        if (v < ntun) {
+            const uint32_t k = tun[v].key_id;
+            lo = min(lo, k);
+            hi = max(hi, k);
+            any = true;
+        }
+    }
+    if (any) {
+        atomicMin(&s_lo, lo);
+        atomicMax(&s_hi, hi);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *h_key = s_lo == s_hi ? s_lo : (uint32_t)NEB_KEYS_MIXED;
+}
+
+__global__ __launch_bounds__(256) void tx_via_fix_kernel(TxWs ws, int32_t* __restrict__ wire_status) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= ws.nvia[0]) return;
+    const int32_t st = ws.via_status[j];
+    if (st != NEB_STATUS_OK) wire_status[ws.via_map[j]] = st;
+}
+
 }  // namespace neb
 
 // ------------------------------------------------------------------------------------------
@@ -788,9 +1005,10 @@ extern "C" size_t neb_tx_ws_bytes(uint32_t n, uint32_t ntun, uint32_t max_wires,
 #endif
 
 extern "C" hipError_t neb_tx_plan(const neb_tx_packet* d_pk, uint32_t n, const uint8_t* d_in,
-                                  neb_tx_tunnel* d_tun, uint32_t ntun, const uint32_t* d_keys, uint32_t max_keys,
-                                  int alg, const neb::TxWs* ws, uint64_t out_cap, uint32_t max_wires,
-                                  int32_t* d_pk_status, uint32_t* d_nwires, hipStream_t s) {
+                                  neb_tx_tunnel* d_tun, uint32_t ntun, const neb_relay_route* d_via,
+                                  const uint32_t* d_keys, uint32_t max_keys, int alg, const neb::TxWs* ws,
+                                  uint64_t out_cap, uint32_t max_wires, int32_t* d_pk_status, uint32_t* d_nwires,
+                                  hipStream_t s) {
     int bits = 1;
     while (bits < 32 && (1ull << bits) <= ntun) bits++;
     if (NEB_TX_SMALL_PLAN && n <= neb::kTxPlanSmallMax) {
@@ -800,24 +1018,29 @@ extern "C" hipError_t neb_tx_plan(const neb_tx_packet* d_pk, uint32_t n, const u
         if (pre) {
             const uint32_t tpb = 256;
             hipLaunchKernelGGL(neb::tx_parse_kernel, dim3((n + tpb - 1) / tpb), dim3(tpb), 0, s, d_pk, n, d_in, d_tun,
-                               ntun, d_keys, max_keys, alg, *ws, d_pk_status);
+                               ntun, d_via, d_keys, max_keys, alg, *ws, d_pk_status);
         }
         // the block sort and scans cost by items per thread: 2 up to 2048 reads
         auto plan = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(1), dim3(neb::kTxPlanThreads), 0, s, d_pk, n, d_in, d_tun, ntun, d_keys,
+            hipLaunchKernelGGL(kern, dim3(1), dim3(neb::kTxPlanThreads), 0, s, d_pk, n, d_in, d_tun, ntun, d_via, d_keys,
                                max_keys, alg, out_cap, max_wires, bits, *ws, d_pk_status, d_nwires);
         };
-        if (n <= 2u * neb::kTxPlanThreads)
-            pre ? plan(neb::tx_plan_small_kernel<2, true>) : plan(neb::tx_plan_small_kernel<2, false>);
+        if (d_via) {
+            if (n <= 2u * neb::kTxPlanThreads)
+                pre ? plan(neb::tx_plan_small_kernel<2, true, true>) : plan(neb::tx_plan_small_kernel<2, false, true>);
+            else
+                plan(neb::tx_plan_small_kernel<neb::kTxPlanItems, true, true>);
+        } else if (n <= 2u * neb::kTxPlanThreads)
+            pre ? plan(neb::tx_plan_small_kernel<2, true, false>) : plan(neb::tx_plan_small_kernel<2, false, false>);
         else
-            plan(neb::tx_plan_small_kernel<neb::kTxPlanItems, true>);
+            plan(neb::tx_plan_small_kernel<neb::kTxPlanItems, true, false>);
         hipLaunchKernelGGL(neb::tx_segmap_kernel, dim3((n + 3) / 4), dim3(256), 0, s, n, max_wires, out_cap, *ws);
         return hipGetLastError();
     }
     const uint32_t tpb = 256, grid = (n + tpb - 1) / tpb;
     hipError_t e = hipMemsetAsync(ws->tun_total, 0, (size_t)ntun * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(neb::tx_parse_kernel, dim3(grid), dim3(tpb), 0, s, d_pk, n, d_in, d_tun, ntun, d_keys,
+    hipLaunchKernelGGL(neb::tx_parse_kernel, dim3(grid), dim3(tpb), 0, s, d_pk, n, d_in, d_tun, ntun, d_via, d_keys,
                        max_keys, alg, *ws, d_pk_status);
     size_t cb = ws->cub_bytes;
     e = hipcub::DeviceScan::ExclusiveSum(ws->cub_tmp, cb, ws->scan_in, ws->scan_out, (int)n, s);
@@ -826,21 +1049,37 @@ extern "C" hipError_t neb_tx_plan(const neb_tx_packet* d_pk, uint32_t n, const u
     e = hipcub::DeviceRadixSort::SortPairs(ws->cub_tmp, cb, ws->tun_key, ws->tun_key_sorted, ws->idx, ws->idx_sorted,
                                            (int)n, 0, bits, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(neb::tx_gather_kernel, dim3(grid), dim3(tpb), 0, s, n, *ws);
+    hipLaunchKernelGGL(neb::tx_gather_kernel<false>, dim3(grid), dim3(tpb), 0, s, n, *ws);
     cb = ws->cub_bytes;
     e = hipcub::DeviceScan::ExclusiveSumByKey(ws->cub_tmp, cb, ws->tun_key_sorted, ws->nseg_sorted, ws->ctr_sorted,
                                               (int)n, hipcub::Equality(), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(neb::tx_scatter_kernel, dim3(grid), dim3(tpb), 0, s, n, d_tun, ntun, out_cap, max_wires, *ws,
-                       d_pk_status, d_nwires);
+    hipLaunchKernelGGL(neb::tx_scatter_kernel<false>, dim3(grid), dim3(tpb), 0, s, n, d_tun, ntun, out_cap, max_wires,
+                       *ws, d_pk_status, d_nwires);
+    if (d_via) {
+        // the second level: the same sort and scan with every via read keyed by its relay tunnel and
+        // weighted by its outer counters (known from its first inner counter)
+        hipLaunchKernelGGL(neb::tx_via_rekey_kernel, dim3(grid), dim3(tpb), 0, s, n, *ws);
+        cb = ws->cub_bytes;
+        e = hipcub::DeviceRadixSort::SortPairs(ws->cub_tmp, cb, ws->tun_key, ws->tun_key_sorted, ws->idx, ws->idx_sorted,
+                                               (int)n, 0, bits, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(neb::tx_gather_kernel<true>, dim3(grid), dim3(tpb), 0, s, n, *ws);
+        cb = ws->cub_bytes;
+        e = hipcub::DeviceScan::ExclusiveSumByKey(ws->cub_tmp, cb, ws->tun_key_sorted, ws->nseg_sorted, ws->ctr_sorted,
+                                                  (int)n, hipcub::Equality(), s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(neb::tx_scatter_kernel<true>, dim3(grid), dim3(tpb), 0, s, n, d_tun, ntun, out_cap,
+                           max_wires, *ws, d_pk_status, d_nwires);
+    }
     hipLaunchKernelGGL(neb::tx_segmap_kernel, dim3((n + 3) / 4), dim3(256), 0, s, n, max_wires, out_cap, *ws);
     return hipGetLastError();
 }
 
 extern "C" hipError_t neb_tx_segment(const neb_tx_packet* d_pk, uint32_t n, const uint8_t* d_in,
-                                     const neb_tx_tunnel* d_tun, uint8_t* d_out, const neb::TxWs* ws,
-                                     neb_tx_wire* d_wires, const uint32_t* d_nwires, uint32_t max_wires, int cu_count,
-                                     uint32_t cs_slots, hipStream_t s) {
+                                     const neb_tx_tunnel* d_tun, const neb_relay_route* d_via, uint8_t* d_out,
+                                     const neb::TxWs* ws, neb_tx_wire* d_wires, const uint32_t* d_nwires,
+                                     uint32_t max_wires, int cu_count, uint32_t cs_slots, hipStream_t s) {
     (void)n;
     const uint32_t per_block = neb::kTxWaves * 64u / neb::kTxGroup;
     const uint32_t want = (max_wires + per_block - 1) / per_block;
@@ -850,12 +1089,26 @@ extern "C" hipError_t neb_tx_segment(const neb_tx_packet* d_pk, uint32_t n, cons
     const uint32_t cap = (uint32_t)cu_count * NEB_TX_SEG_CAP;
     const uint32_t grid = want < cap ? want : cap;
     if (grid == 0) return hipSuccess;
-    if (cs_slots)
-        hipLaunchKernelGGL(neb::tx_segment_kernel<true>, dim3(grid), dim3(neb::kTxWaves * 64), 0, s, d_pk, d_in, d_tun,
-                           d_out, *ws, d_wires, d_nwires, cs_slots);
+    auto seg = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(neb::kTxWaves * 64), 0, s, d_pk, d_in, d_tun, d_via, d_out, *ws,
+                           d_wires, d_nwires, cs_slots);
+    };
+    if (d_via)
+        cs_slots ? seg(neb::tx_segment_kernel<true, true>) : seg(neb::tx_segment_kernel<false, true>);
     else
-        hipLaunchKernelGGL(neb::tx_segment_kernel<false>, dim3(grid), dim3(neb::kTxWaves * 64), 0, s, d_pk, d_in, d_tun,
-                           d_out, *ws, d_wires, d_nwires, cs_slots);
+        cs_slots ? seg(neb::tx_segment_kernel<true, false>) : seg(neb::tx_segment_kernel<false, false>);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t neb_tx_via_key(const neb_tx_tunnel* d_tun, uint32_t ntun, const neb_relay_route* d_via,
+                                     uint32_t* h_key, hipStream_t s) {
+    hipLaunchKernelGGL(neb::tx_via_key_kernel, dim3(1), dim3(1024), 0, s, d_tun, ntun, d_via, h_key);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t neb_tx_via_fix(const neb::TxWs* ws, uint32_t max_wires, int32_t* d_wire_status, hipStream_t s) {
+    if (max_wires == 0) return hipSuccess;
+    hipLaunchKernelGGL(neb::tx_via_fix_kernel, dim3((max_wires + 255u) / 256u), dim3(256), 0, s, *ws, d_wire_status);
     return hipGetLastError();
 }
 

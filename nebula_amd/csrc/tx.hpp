@@ -29,7 +29,8 @@ struct TxPlan {          // per packet (tx_parse_kernel)
     uint32_t nseg;       // 0 = dropped
     uint32_t hdr_len;    // superpackets: the corrected L3+L4 header length
     uint32_t full_slot;  // output bytes of one full-size segment (16-aligned)
-    uint8_t kind, v4, fl0, pad0;
+    uint8_t kind, v4, fl0;
+    uint8_t via;         // sent through a relay (neb_tx_seal_via_batch): full_slot has the 32 bytes more
     // per-superpacket constants of the segment headers (segment_linux.go:166-208), computed once
     uint32_t ip_base;    // baseIPv4HdrSum
     uint32_t l4_base;    // TCP: baseTCPHdrSum + basePseudoSum; UDP: basePseudoSum
@@ -53,6 +54,14 @@ struct TxWs {
     unsigned long long* tun_total;  // per tunnel: segments in this batch
     unsigned long long* totals;     // [0] segments, [1] bytes of the fitting prefix
     neb_desc* seal_desc;         // per wire
+    // through a relay (neb_tx_seal_via_batch): the second counter level and the outer seal's batch
+    uint32_t* via_tun;           // per packet: its relay tunnel (NEB_RELAY_NONE: sent directly)
+    uint64_t* via_ctr_base;      // per via packet: the relay tunnel's counter before its first outer header
+    uint32_t* via_pos;           // per via packet: its first outer descriptor in via_desc
+    neb_desc* via_desc;          // the outer AD-only seals, compacted
+    uint32_t* via_map;           // their wires
+    int32_t* via_status;
+    uint32_t* nvia;              // the number of outer seals
     void* cub_tmp;
     size_t cub_bytes;
 };
@@ -82,6 +91,13 @@ inline size_t tx_ws_layout(uint32_t n, uint32_t ntun, uint32_t max_wires, size_t
     w.totals = (unsigned long long*)take(16);
     w.seal_desc = (neb_desc*)take((size_t)(max_wires ? max_wires : 1) * sizeof(neb_desc));
     w.seg_pkt = (uint32_t*)take((size_t)(max_wires ? max_wires : 1) * 4);
+    w.via_tun = (uint32_t*)take((size_t)n * 4);
+    w.via_ctr_base = (uint64_t*)take((size_t)n * 8);
+    w.via_pos = (uint32_t*)take((size_t)n * 4);
+    w.via_desc = (neb_desc*)take((size_t)(max_wires ? max_wires : 1) * sizeof(neb_desc));
+    w.via_map = (uint32_t*)take((size_t)(max_wires ? max_wires : 1) * 4);
+    w.via_status = (int32_t*)take((size_t)(max_wires ? max_wires : 1) * 4);
+    w.nvia = (uint32_t*)take(4);
     w.cub_tmp = take(cub_bytes);
     w.cub_bytes = cub_bytes;
     if (ws) *ws = w;
@@ -92,14 +108,23 @@ inline size_t tx_ws_layout(uint32_t n, uint32_t ntun, uint32_t max_wires, size_t
 
 extern "C" size_t neb_tx_ws_bytes(uint32_t n, uint32_t ntun, uint32_t max_wires, size_t* cub_bytes);
 // Plans the batch; for n <= kTxPlanSmallMax it also advances the tunnels' message counters
-// (neb_tx_finish is then a no-op to skip).
+// (neb_tx_finish is then a no-op to skip). d_via (optional): the tunnels' relays
+// (neb_tx_seal_via_batch); the plan then also assigns the relay tunnels' counters and the outer
+// seal's compacted positions (ws->nvia).
 extern "C" hipError_t neb_tx_plan(const neb_tx_packet* d_pk, uint32_t n, const uint8_t* d_in,
-                                  neb_tx_tunnel* d_tun, uint32_t ntun, const uint32_t* d_keys, uint32_t max_keys,
-                                  int alg, const neb::TxWs* ws, uint64_t out_cap, uint32_t max_wires,
-                                  int32_t* d_pk_status, uint32_t* d_nwires, hipStream_t s);
+                                  neb_tx_tunnel* d_tun, uint32_t ntun, const neb_relay_route* d_via,
+                                  const uint32_t* d_keys, uint32_t max_keys, int alg, const neb::TxWs* ws,
+                                  uint64_t out_cap, uint32_t max_wires, int32_t* d_pk_status, uint32_t* d_nwires,
+                                  hipStream_t s);
 extern "C" hipError_t neb_tx_segment(const neb_tx_packet* d_pk, uint32_t n, const uint8_t* d_in,
-                                     const neb_tx_tunnel* d_tun, uint8_t* d_out, const neb::TxWs* ws,
-                                     neb_tx_wire* d_wires, const uint32_t* d_nwires, uint32_t max_wires, int cu_count,
-                                     uint32_t cs_slots, hipStream_t s);
+                                     const neb_tx_tunnel* d_tun, const neb_relay_route* d_via, uint8_t* d_out,
+                                     const neb::TxWs* ws, neb_tx_wire* d_wires, const uint32_t* d_nwires,
+                                     uint32_t max_wires, int cu_count, uint32_t cs_slots, hipStream_t s);
+// *h_key (pinned host memory, written by the kernel) = the one key of the relay tunnels d_via names,
+// NEB_KEYS_MIXED when they have several (or none is named); independent of the plan.
+extern "C" hipError_t neb_tx_via_key(const neb_tx_tunnel* d_tun, uint32_t ntun, const neb_relay_route* d_via,
+                                     uint32_t* h_key, hipStream_t s);
+// After the outer seal: a via wire it refused (the relay key destroyed meanwhile) gets its status.
+extern "C" hipError_t neb_tx_via_fix(const neb::TxWs* ws, uint32_t max_wires, int32_t* d_wire_status, hipStream_t s);
 extern "C" hipError_t neb_tx_finish(neb_tx_tunnel* d_tun, uint32_t n, uint32_t ntun, const neb::TxWs* ws,
                                     hipStream_t s);

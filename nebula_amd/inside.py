@@ -1,8 +1,11 @@
 """Host-side mirror of Nebula's transmit path for a batch of TUN reads, on the engine's device
-TX batch (neb_tx_seal_batch[_host], nebula_amd/csrc/tx.hip).
+TX batch (neb_tx_seal_batch[_host], and through relays neb_tx_seal_via_batch[_host];
+nebula_amd/csrc/tx.hip).
 
 Reference (slackhq/nebula):
   inside.go:154-240         sendInsideMessage: SegmentSuperpacket, one Reserve(16+len+16) slot per segment
+  inside.go:178-223         its relay branch: the segment sealed at scratch[16:], then prepareSendVia
+  inside.go:442-501         prepareSendVia: the relay tunnel's counter, a Message/Relay header, a second tag
   inside.go:123-146         sendInsideEncrypt: messageCounter.Add(1), header.Encode, EncryptDanger; a refused
                             segment is dropped (its counter stays used)
   overlay/tio/tio_gso_linux.go:231-280   decodeRead (virtio_net_hdr checks, FinishChecksum)
@@ -41,6 +44,19 @@ def slot_bytes(seg_len: int) -> int:
     return (seg_len + 32 + 15) & ~15
 
 
+def slot_bytes_via(seg_len: int) -> int:
+    """Output bytes of one wire packet sent through a relay (relay header ‖ header ‖ ct ‖ tag ‖ relay
+    tag), 16-byte aligned."""
+    return (seg_len + 64 + 15) & ~15
+
+
+def _via_array(via, ntunnels: int) -> np.ndarray:
+    via = np.ascontiguousarray(via, dtype=L.RELAY_ROUTE_DTYPE)
+    if len(via) != ntunnels:
+        raise ValueError("via needs one neb_relay_route per tunnel")
+    return via
+
+
 @dataclass
 class TxResult:
     out: np.ndarray          # output arena
@@ -75,13 +91,37 @@ def tx_seal_batch_host(engine, alg: int, tunnels: np.ndarray, packets: np.ndarra
     return TxResult(out, wires[:n].copy(), wst[:n].copy(), pst, tunnels)
 
 
+def tx_seal_via_batch_host(engine, alg: int, tunnels: np.ndarray, via, packets: np.ndarray, in_arena: np.ndarray,
+                           out_cap: int, max_wires: int, key_hint: int = L.KEYS_MIXED) -> TxResult:
+    """sendInsideMessage with its relay branch over a batch of TUN reads in host memory: via[t]
+    (RELAY_ROUTE_DTYPE) names the relay tunnel of tunnel t, RELAY_NONE = sent directly; via=None:
+    every tunnel is direct. A via wire has TX_WIRE_VIA in wires["reserved"]."""
+    lib = L.lib()
+    tunnels = np.ascontiguousarray(tunnels, dtype=TX_TUNNEL_DTYPE).copy()
+    via = None if via is None else _via_array(via, len(tunnels))
+    packets = np.ascontiguousarray(packets, dtype=TX_PACKET_DTYPE)
+    in_arena = np.ascontiguousarray(in_arena, dtype=np.uint8)
+    out = np.zeros(out_cap, np.uint8)
+    wires = np.zeros(max_wires, TX_WIRE_DTYPE)
+    wst = np.zeros(max_wires, np.int32)
+    pst = np.zeros(len(packets), np.int32)
+    nw = C.c_uint32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = lib.neb_tx_seal_via_batch_host(engine.handle, alg, vp(tunnels), len(tunnels), None if via is None else vp(via),
+                                        vp(packets), len(packets), vp(in_arena), in_arena.nbytes, vp(out), out_cap,
+                                        vp(wires), vp(wst), max_wires, C.byref(nw), vp(pst), key_hint)
+    L.check(rc, "neb_tx_seal_via_batch_host")
+    n = nw.value
+    return TxResult(out, wires[:n].copy(), wst[:n].copy(), pst, tunnels)
+
+
 class DeviceTxBatch:
     """A TX batch resident in device memory (torch tensors as plain allocations): the input arena
     of TUN reads, the tunnel table and the output arena; `seal()` runs neb_tx_seal_batch on torch's
-    current stream."""
+    current stream; with `via` (one RELAY_ROUTE_DTYPE entry per tunnel) neb_tx_seal_via_batch."""
 
     def __init__(self, engine, alg: int, tunnels: np.ndarray, packets: np.ndarray, in_arena: np.ndarray,
-                 out_cap: int, max_wires: int, key_hint: int = L.KEYS_MIXED):
+                 out_cap: int, max_wires: int, key_hint: int = L.KEYS_MIXED, via=None):
         import torch
 
         dev = torch.device("cuda", engine.device)
@@ -98,6 +138,9 @@ class DeviceTxBatch:
         self.pk_status = torch.zeros(self.npk, dtype=torch.int32, device=dev)
         self.nwires = torch.zeros(1, dtype=torch.int32, device=dev)
         self.max_wires = max_wires
+        self.via = None
+        if via is not None:
+            self.via = torch.from_numpy(_via_array(via, self.ntun).view(np.uint8).copy()).to(dev)
 
     def reset_counters(self) -> None:
         import torch
@@ -109,6 +152,14 @@ class DeviceTxBatch:
 
         lib = L.lib()
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        if self.via is not None:
+            rc = lib.neb_tx_seal_via_batch(self.engine.handle, self.alg, p(self.tunnels), self.ntun, p(self.via),
+                                           p(self.packets), self.npk, p(self.inp), p(self.out), self.out.numel(),
+                                           p(self.wires), p(self.wire_status), self.max_wires, p(self.nwires),
+                                           p(self.pk_status), self.key_hint,
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            L.check(rc, "neb_tx_seal_via_batch")
+            return
         rc = lib.neb_tx_seal_batch(self.engine.handle, self.alg, p(self.tunnels), self.ntun, p(self.packets),
                                    self.npk, p(self.inp), p(self.out), self.out.numel(), p(self.wires),
                                    p(self.wire_status), self.max_wires, p(self.nwires), p(self.pk_status),
@@ -122,5 +173,5 @@ class DeviceTxBatch:
                         self.pk_status.cpu().numpy(), self.tunnels.cpu().numpy().view(TX_TUNNEL_DTYPE).copy())
 
 
-__all__ = ["TX_PACKET_DTYPE", "TX_TUNNEL_DTYPE", "TX_WIRE_DTYPE", "tx_seal_batch_host", "DeviceTxBatch", "TxResult",
-           "slot_bytes"]
+__all__ = ["TX_PACKET_DTYPE", "TX_TUNNEL_DTYPE", "TX_WIRE_DTYPE", "tx_seal_batch_host", "tx_seal_via_batch_host",
+           "DeviceTxBatch", "TxResult", "slot_bytes", "slot_bytes_via"]
