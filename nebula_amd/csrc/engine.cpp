@@ -15,7 +15,6 @@
 #include <cxxabi.h>
 #include <cstdlib>
 #include <climits>
-#include <dlfcn.h>
 #include <linux/futex.h>
 #include <mutex>
 #include <new>
@@ -36,6 +35,7 @@
 #include "timing.hpp"
 #include "tx.hpp"
 #include "coalesce.hpp"
+#include "engine_internal.hpp"
 
 // n keys (32 B each, mapped host memory) into the records of key slots slots[0..n): one launch
 extern "C" hipError_t neb_gcm_key_setup(const uint8_t* keys, const uint32_t* slots, uint32_t n, uint32_t* table,
@@ -74,41 +74,12 @@ extern "C" hipError_t neb_chacha_batch(int open, const neb_desc* d_desc, uint32_
                                        int32_t* d_status, const uint32_t* d_n, int cu_count, hipStream_t s,
                                        int hdr_from_dst, hipEvent_t stop, const uint8_t* rx);
 
-// The stream a workspace's `done` event was last recorded on. A batch on that same stream is
-// ordered after it already and skips the cross-stream wait (a barrier packet that cost ≈ 5 µs between
-// kernels). The handle alone does not name a stream: one destroyed with work still pending is
-// released when the work ends, and a stream created meanwhile may get its address; so the identity
-// is the handle together with HIP's per-stream id (hipStreamGetId, HIP >= 7.1, looked up at run time:
-// a process may run an older HIP runtime, as PyTorch's wheel does). Without it the handle alone is
-// the identity, and a caller must not destroy a stream while the engine's batches on it are pending
-// (streams).
-struct StreamTag {
-    using GetId = hipError_t (*)(hipStream_t, unsigned long long*);
-    hipStream_t h = nullptr;
-    unsigned long long id = 0;
-    bool valid = false;
-    static unsigned long long id_of(hipStream_t s) {
-        static const GetId get = (GetId)dlsym(RTLD_DEFAULT, "hipStreamGetId");
-        unsigned long long v = 0;
-        return get && get(s, &v) == hipSuccess ? v : 0ull;
-    }
-    bool same(hipStream_t s) const { return valid && h == s && id_of(s) == id; }
-    void set(hipStream_t s) {
-        h = s;
-        id = id_of(s);
-        valid = true;
-    }
-};
-
-// Device workspace of the mixed-key scheduler (sched.hpp). One per engine; a batch waits on the
-// previous user's event before reusing it, so batches on different streams never overlap in it.
+// Device workspace of the mixed-key scheduler (sched.hpp). One per engine (and per queue batch,
+// receive slot and window set); batches on different streams never overlap in it (workspace.hpp).
 struct SchedSpace {
-    uint8_t* mem = nullptr;
-    size_t bytes = 0;
+    neb::HipWorkspace<> dev;
     uint32_t n_cap = 0;
     neb::SchedWs ws{};
-    hipEvent_t done = nullptr;
-    StreamTag last;  // the stream `done` was last recorded on
     bool dirty = true;  // the bin counts need a clear (new buffer, or a batch that failed to launch)
     std::mutex mu;
 };
@@ -172,12 +143,6 @@ struct Pipe {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-
-}  // namespace
-
-
-namespace {
-
 // Host batch path: NEB_HOST_MODE = "zc" (the kernels on the mapped arena, the default) or "dma"
 // (hipMemcpyAsync staging); NEB_HOST_STAGED=1 is the older name of "dma". Measured on one MI355X
 // (C2 seal+open, 64 Ki x 1300 B): zero-copy 28.4 GiB/s against 23.9 for DMA staging.
@@ -190,14 +155,10 @@ HostMode host_mode() {  // NEB_KNOB_HOST_MODE, read per batch, so a process can 
 
 // Device workspace of the transmit batch (tx.hpp) plus device staging for its host-memory form.
 struct TxSpace {
-    uint8_t* mem = nullptr;
-    size_t bytes = 0;
+    enum { kWs, kIo };  // dev's buffers: the workspace, neb_tx_seal_batch_host's staging
+    neb::HipWorkspace<2> dev;
     uint32_t n_cap = 0, tun_cap = 0, wire_cap = 0;
     neb::TxWs ws{};
-    hipEvent_t done = nullptr;
-    StreamTag last;  // the stream `done` was last recorded on
-    uint8_t* d_io = nullptr;  // neb_tx_seal_batch_host staging
-    size_t io_cap = 0;
     // through a relay (neb_tx_seal_via_batch): the relay tunnels' one key, read back for the outer seal
     uint32_t* h_via_key = nullptr;  // pinned
     hipEvent_t via_ev = nullptr;
@@ -206,11 +167,9 @@ struct TxSpace {
 
 // Device workspace of the receive coalescer (coalesce.hpp).
 struct CoSpace {
-    uint8_t* mem = nullptr;
+    neb::HipWorkspace<> dev;
     uint32_t n_cap = 0;
     neb::CoWs ws{};
-    hipEvent_t done = nullptr;
-    StreamTag last;
     std::mutex mu;
 };
 
@@ -625,28 +584,17 @@ NEB_API int neb_engine_destroy(neb_engine* e) {
         if (s.d_desc) hipFree(s.d_desc);
         if (s.h_status) hipHostFree(s.h_status);
     }
-    if (SchedSpace* sp = e->pipe.sched) {
-        if (sp->done) { hipEventSynchronize(sp->done); hipEventDestroy(sp->done); }
-        if (sp->mem) hipFree(sp->mem);
-        delete sp;
-    }
-    if (e->sched.done) { hipEventSynchronize(e->sched.done); hipEventDestroy(e->sched.done); }
-    if (e->sched.mem) hipFree(e->sched.mem);
-    if (e->tx.done) { hipEventSynchronize(e->tx.done); hipEventDestroy(e->tx.done); }
-    if (e->tx.mem) hipFree(e->tx.mem);
-    if (e->tx.d_io) hipFree(e->tx.d_io);
+    // the workspaces (each waits for its last batch) here, with the device current, not in ~neb_engine
+    neb_sched_space_free(e->pipe.sched);
+    e->sched.dev.destroy();
+    e->tx.dev.destroy();
     if (e->tx.h_via_key) hipHostFree(e->tx.h_via_key);
     if (e->tx.via_ev) hipEventDestroy(e->tx.via_ev);
-    if (e->co.done) { hipEventSynchronize(e->co.done); hipEventDestroy(e->co.done); }
-    if (e->co.mem) hipFree(e->co.mem);
+    e->co.dev.destroy();
     for (auto& r : e->rx.slot) {
         if (r.stream) { hipStreamSynchronize(r.stream); hipStreamDestroy(r.stream); }
         if (r.ev) hipEventDestroy(r.ev);
-        if (r.sched) {
-            if (r.sched->done) { hipEventSynchronize(r.sched->done); hipEventDestroy(r.sched->done); }
-            if (r.sched->mem) hipFree(r.sched->mem);
-            delete r.sched;
-        }
+        neb_sched_space_free(r.sched);
     }
     if (e->rx.h_desc) hipHostFree(e->rx.h_desc);
     if (e->rx.h_status) hipHostFree(e->rx.h_status);
@@ -874,7 +822,7 @@ NEB_API int neb_cipher_destroy(neb_cipher* c) {
     }
     {
         std::lock_guard<std::mutex> g(e->sched.mu);
-        if (e->sched.done) wait.push_back(e->sched.done);
+        if (e->sched.dev.event()) wait.push_back(e->sched.dev.event());
     }
     for (hipEvent_t ev : wait) (void)hipEventSynchronize(ev);
     int rc = NEB_OK;
@@ -915,19 +863,13 @@ static void fill_nonce(int alg, uint64_t n, uint8_t* nb) {
 // does not wait for, and may still be running when the binning starts (measured: the first batches
 // of a queue lost most of their packets' statuses to it).
 static hipError_t sched_reserve(neb_engine* e, SchedSpace& sp, uint32_t n, hipStream_t s) {
-    if (!sp.done) {
-        // ordering only (the host and other streams wait for the kernels, nobody reads the
-        // workspace from the host): no system-scope cache release at each record
-        hipError_t err = hipEventCreateWithFlags(&sp.done, hipEventDisableTiming | hipEventDisableSystemFence);
-        if (err != hipSuccess) return err;
-    }
     // the tile binning's arrays (sched.hpp), only for workspaces that see batches that large: a
     // queue's small batches keep the atomic histogram and need none
     const bool tiles = (int64_t)n >= neb::knob(NEB_KNOB_TILE_BINS_FROM) || sp.ws.tcnt;
-    const bool fits = n <= sp.n_cap && sp.mem && (!tiles || sp.ws.tcnt);
+    const bool fits = n <= sp.n_cap && sp.dev.mem() && (!tiles || sp.ws.tcnt);
     if (fits && !sp.dirty) return hipSuccess;
     if (fits) {  // the bins are cleared as they are consumed, except after a failure
-        hipError_t err = hipEventSynchronize(sp.done);
+        hipError_t err = sp.dev.sync();
         if (err == hipSuccess)
             err = hipMemsetAsync(sp.ws.counters, 0, (neb::kSchedCounters + (size_t)neb::kSubBins * neb::sched_nbins(e->max_keys)) * 4u, s);
         if (err == hipSuccess) sp.dirty = false;
@@ -942,37 +884,27 @@ static hipError_t sched_reserve(neb_engine* e, SchedSpace& sp, uint32_t n, hipSt
     const size_t b_tcnt = tiles ? align_up((size_t)neb::kTileMax * neb::sched_tile_words(nb) * 4u, 256) : 0;
     const size_t b_tpre = tiles ? align_up((size_t)neb::kTileMax * nb * 4u, 256) : 0;
     const size_t bytes = b_counters + b_base + 3 * b_idx + b_chunks + b_tcnt + b_tpre;
-    hipError_t err = hipEventSynchronize(sp.done);  // the old buffer may still be in use
-    if (err != hipSuccess) return err;
-    if (sp.mem) hipFree(sp.mem);
-    sp.mem = nullptr;
     sp.n_cap = 0;
-    err = hipMalloc((void**)&sp.mem, bytes);
+    bool grew = false;
+    hipError_t err = sp.dev.reserve(bytes, &grew);
+    if (err == hipSuccess && !grew) err = sp.dev.sync();  // (as many bytes, laid out again: as after growing)
     if (err != hipSuccess) return err;
-    uint8_t* m = sp.mem;
-    sp.ws.counters = (uint32_t*)m;
+    uint8_t* m = sp.dev.mem();
+    auto take = [&m](size_t b) { return (m += b) - b; };  // the next b bytes
+    sp.ws.counters = (uint32_t*)take(b_counters);
     sp.ws.hist = sp.ws.counters + neb::kSchedCounters;
-    m += b_counters;
-    sp.ws.base = (uint32_t*)m;
-    m += b_base;
-    sp.ws.binof = (uint32_t*)m;
-    m += b_idx;
-    sp.ws.binpos = (uint32_t*)m;
-    m += b_idx;
-    sp.ws.sorted = (uint32_t*)m;
-    m += b_idx;
-    sp.ws.chunks = (uint4*)m;
-    m += b_chunks;
-    sp.ws.tcnt = tiles ? (uint32_t*)m : nullptr;
-    m += b_tcnt;
-    sp.ws.tpre = tiles ? (uint32_t*)m : nullptr;
+    sp.ws.base = (uint32_t*)take(b_base);
+    sp.ws.binof = (uint32_t*)take(b_idx);
+    sp.ws.binpos = (uint32_t*)take(b_idx);
+    sp.ws.sorted = (uint32_t*)take(b_idx);
+    sp.ws.chunks = (uint4*)take(b_chunks);
+    sp.ws.tcnt = tiles ? (uint32_t*)take(b_tcnt) : nullptr;
+    sp.ws.tpre = tiles ? (uint32_t*)take(b_tpre) : nullptr;
     sp.ws.max_chunks = mc;
-    sp.bytes = bytes;
     sp.n_cap = cap;
     err = hipMemsetAsync(sp.ws.counters, 0, b_counters, s);  // once: the binning clears its counts as it uses them
-    if (err != hipSuccess) return err;
-    sp.dirty = false;
-    return hipSuccess;
+    if (err == hipSuccess) sp.dirty = false;
+    return err;
 }
 
 // Groups per front chunk at most (sched_groups' own: up to 8) for a batch of n packets: below
@@ -1014,21 +946,21 @@ static hipError_t launch_batch(neb_engine* e, int alg, int open, const neb_desc*
         hipError_t err = hipSuccess;
         if (!prebinned) {
             err = sched_reserve(e, sp, n, s);
-            if (err == hipSuccess && !sp.last.same(s)) err = hipStreamWaitEvent(s, sp.done, 0);  // the previous batch on it
+            if (err == hipSuccess) err = sp.dev.begin(s);  // after the previous batch on it
             neb::SchedWs ws = sp.ws;
             ws.max_groups = front_groups(e, n);
             if (err == hipSuccess) err = neb_sched_build(d_desc, n, d_n, e->max_keys, 4u, &ws, s);
         }
-        if (err == hipSuccess)  // sp.done bound to the chunk kernel's dispatch: no marker packet between batches
+        if (err == hipSuccess)  // the workspace's event bound to the chunk kernel's dispatch: no marker packet between batches
             err = neb_gcm_batch_chunked(open, d_desc, n, d_arena, e->d_keys, e->max_keys, d_status, sp.ws.sorted,
                                         sp.ws.chunks, sp.ws.counters, sp.ws.max_chunks, e->cu_count,
-                                        s, hdr_from_dst, bind_events() ? sp.done : nullptr,
+                                        s, hdr_from_dst, bind_events() ? sp.dev.event() : nullptr,
                                         prebinned ? nullptr : rx);  // (prebinned: refused packets unlisted)
-        if (err == hipSuccess && !bind_events()) err = hipEventRecord(sp.done, s);
-        if (err == hipSuccess) sp.last.set(s);
+        if (err == hipSuccess && bind_events()) sp.dev.end_bound(s);
+        else if (err == hipSuccess) err = sp.dev.end(s);
         if (err != hipSuccess) {
             // binning passes of this batch may already be queued on s: let them finish before the
-            // next batch clears the counters (sched_reserve's dirty path waits on sp.done only)
+            // next batch clears the counters (sched_reserve's dirty path waits on the event only)
             (void)hipStreamSynchronize(s);
             sp.dirty = true;
         }
@@ -1367,10 +1299,10 @@ int neb_check_batch_args(neb_engine* e, int alg, uint32_t key_hint) { return che
 // Open the first *d_n (a count in device memory) of at most n descriptors, on stream s.
 int neb_open_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
                          uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s, const uint8_t* rx,
-                         void* prebinned) {
+                         SchedSpace* prebinned) {
     if (n == 0) return NEB_OK;
-    hipError_t err = launch_batch(e, alg, 1, d_desc, n, d_arena, d_status, key_hint, s, d_n,
-                                  static_cast<SchedSpace*>(prebinned), 0, nullptr, rx, prebinned != nullptr);
+    hipError_t err = launch_batch(e, alg, 1, d_desc, n, d_arena, d_status, key_hint, s, d_n, prebinned, 0, nullptr,
+                                  rx, prebinned != nullptr);
     if (err != hipSuccess) {
         set_error("batch launch", err);
         return NEB_ERR_HIP;
@@ -1398,18 +1330,20 @@ int neb_seal_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_
 
 // For the submission queue (queue.cpp): a scheduler workspace of its own, and a launch of one
 // staged batch (zero-copy on pinned memory) on the queue's stream.
-void* neb_sched_space_new() { return new (std::nothrow) SchedSpace; }
+SchedSpace* neb_sched_space_new() { return new (std::nothrow) SchedSpace; }
+void neb_sched_space_free(SchedSpace* sp) { delete sp; }  // ~DevWorkspace waits for the last batch on it
 
 // The device receive (window.cpp): its mixed-key AES-GCM open is binned by extra workgroups of the
 // receive's own plan launches (rxwin.hpp RxBin) into the receive's scheduler workspace `sched`,
 // which this sizes for n packets and orders after its last open; the open then runs with it
 // (neb_open_batch_count's `prebinned`). neb_rx_sched_abort after a failed plan (the counters are
 // then in an unknown state: the next batch clears them).
-int neb_rx_sched_begin(neb_engine* e, uint32_t n, void* sched, hipStream_t s, neb::SchedWs* ws, uint32_t* max_keys) {
-    SchedSpace& sp = *static_cast<SchedSpace*>(sched);
+int neb_rx_sched_begin(neb_engine* e, uint32_t n, SchedSpace* sched, hipStream_t s, neb::SchedWs* ws,
+                       uint32_t* max_keys) {
+    SchedSpace& sp = *sched;
     std::lock_guard<std::mutex> g(sp.mu);
     hipError_t err = sched_reserve(e, sp, n, s);
-    if (err == hipSuccess && !sp.last.same(s)) err = hipStreamWaitEvent(s, sp.done, 0);  // the last open's reads
+    if (err == hipSuccess) err = sp.dev.begin(s);  // after the last open's reads
     if (err != hipSuccess) {
         sp.dirty = true;
         set_error("rx binning", err);
@@ -1420,31 +1354,21 @@ int neb_rx_sched_begin(neb_engine* e, uint32_t n, void* sched, hipStream_t s, ne
     *max_keys = e->max_keys;
     return NEB_OK;
 }
-void neb_rx_sched_abort(void* sched) {
-    SchedSpace& sp = *static_cast<SchedSpace*>(sched);
-    std::lock_guard<std::mutex> g(sp.mu);
-    sp.dirty = true;
-}
-void neb_sched_space_free(void* p) {
-    auto* sp = static_cast<SchedSpace*>(p);
-    if (!sp) return;
-    if (sp->done) { hipEventSynchronize(sp->done); hipEventDestroy(sp->done); }
-    if (sp->mem) hipFree(sp->mem);
-    delete sp;
+void neb_rx_sched_abort(SchedSpace* sched) {
+    std::lock_guard<std::mutex> g(sched->mu);
+    sched->dirty = true;
 }
 int neb_launch_on(neb_engine* e, int alg, int open, const neb_desc* desc, uint32_t n, uint8_t* arena,
-                  int32_t* status, uint32_t key_hint, hipStream_t s, void* sched) {
+                  int32_t* status, uint32_t key_hint, hipStream_t s, SchedSpace* sched) {
     if (n == 0) return NEB_OK;
     DeviceGuard dg(e->device);
-    hipError_t err = launch_batch(e, alg, open, desc, n, arena, status, key_hint, s, nullptr,
-                                  static_cast<SchedSpace*>(sched), 0, nullptr);
+    hipError_t err = launch_batch(e, alg, open, desc, n, arena, status, key_hint, s, nullptr, sched, 0, nullptr);
     if (err != hipSuccess) {
         set_error("queue batch launch", err);
         return NEB_ERR_HIP;
     }
     return NEB_OK;
 }
-bool neb_host_mapped(const void* p);
 int neb_key_alg(neb_engine* e, uint32_t key) {
     std::lock_guard<std::mutex> g(e->key_mu);
     return key < e->max_keys ? e->slot_alg[key] : 0;
@@ -1808,25 +1732,15 @@ void neb_rx_pipe_end(neb_engine* e) {
 
 static hipError_t tx_reserve(neb_engine* e, uint32_t n, uint32_t ntun, uint32_t max_wires) {
     TxSpace& tx = e->tx;
-    if (!tx.done) {
-        // ordering only, as SchedSpace::done: no system-scope cache release at each record
-        hipError_t err = hipEventCreateWithFlags(&tx.done, hipEventDisableTiming | hipEventDisableSystemFence);
-        if (err != hipSuccess) return err;
-    }
-    if (tx.mem && n <= tx.n_cap && ntun <= tx.tun_cap && max_wires <= tx.wire_cap) return hipSuccess;
+    if (tx.dev.mem() && n <= tx.n_cap && ntun <= tx.tun_cap && max_wires <= tx.wire_cap) return hipSuccess;
     const uint32_t nc = std::max({n, tx.n_cap, 1024u}), tc = std::max({ntun, tx.tun_cap, 64u});
     const uint32_t wc = std::max({max_wires, tx.wire_cap, 1024u});
     size_t cub = 0;
     const size_t bytes = neb_tx_ws_bytes(nc, tc, wc, &cub);
-    hipError_t err = hipEventSynchronize(tx.done);  // the old workspace may still be in use
-    if (err != hipSuccess) return err;
-    if (tx.mem) hipFree(tx.mem);
-    tx.mem = nullptr;
     tx.n_cap = tx.tun_cap = tx.wire_cap = 0;
-    err = hipMalloc((void**)&tx.mem, bytes);
+    hipError_t err = tx.dev.reserve(bytes);  // (laid out again whether it grew or not: the capacities changed)
     if (err != hipSuccess) return err;
-    neb::tx_ws_layout(nc, tc, wc, cub, tx.mem, &tx.ws);
-    tx.bytes = bytes;
+    neb::tx_ws_layout(nc, tc, wc, cub, tx.dev.mem(), &tx.ws);
     tx.n_cap = nc;
     tx.tun_cap = tc;
     tx.wire_cap = wc;
@@ -1841,7 +1755,7 @@ static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, c
                   int32_t* d_pk_status, uint32_t key_hint, hipStream_t s) {
     TxSpace& tx = e->tx;
     HIP_TRY(tx_reserve(e, npk, ntun, max_wires));
-    if (!tx.last.same(s)) HIP_TRY(hipStreamWaitEvent(s, tx.done, 0));
+    HIP_TRY(tx.dev.begin(s));
     if (d_via) {
         // the relay tunnels' one key, for a single-key outer seal: asked for first, read back after
         // the inner seal is enqueued, so the host waits for this word only while the device works
@@ -1870,8 +1784,7 @@ static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, c
         HIP_TRY(neb_tx_via_fix(&tx.ws, max_wires, d_wire_status, s));
         note_use(e, hint, s);
     }
-    HIP_TRY(hipEventRecord(tx.done, s));
-    tx.last.set(s);
+    HIP_TRY(tx.dev.end(s));
     return NEB_OK;
 }
 
@@ -1950,16 +1863,8 @@ static int tx_host(neb_engine* e, int alg, neb_tx_tunnel* tunnels, uint32_t ntun
     DeviceGuard dg(e->device);
     TxSpace& tx = e->tx;
     hipStream_t s = e->stream;
-    if (total > tx.io_cap) {
-        if (tx.done) HIP_TRY(hipEventSynchronize(tx.done));
-        if (tx.d_io) hipFree(tx.d_io);
-        tx.d_io = nullptr;
-        tx.io_cap = 0;
-        const size_t cap = align_up(total, 1 << 20);
-        HIP_TRY(hipMalloc((void**)&tx.d_io, cap));
-        tx.io_cap = cap;
-    }
-    uint8_t* d = tx.d_io;
+    HIP_TRY(tx.dev.reserve(align_up(total, 1 << 20), nullptr, TxSpace::kIo));
+    uint8_t* d = tx.dev.mem(TxSpace::kIo);
     auto* d_tun = (neb_tx_tunnel*)(d + o_tun);
     auto* d_pk = (neb_tx_packet*)(d + o_pk);
     auto* d_wires = (neb_tx_wire*)(d + o_w);
@@ -2011,22 +1916,14 @@ NEB_API int neb_tx_seal_via_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tu
 
 static hipError_t co_reserve(neb_engine* e, uint32_t n) {
     CoSpace& co = e->co;
-    if (!co.done) {
-        hipError_t err = hipEventCreateWithFlags(&co.done, hipEventDisableTiming | hipEventDisableSystemFence);
-        if (err != hipSuccess) return err;
-    }
-    if (co.mem && n <= co.n_cap) return hipSuccess;
+    if (co.dev.mem() && n <= co.n_cap) return hipSuccess;
     const uint32_t nc = std::max({n, co.n_cap, 1024u});
     size_t cub = 0;
     const size_t bytes = neb_co_ws_bytes(nc, &cub);
-    hipError_t err = hipEventSynchronize(co.done);  // the old workspace may still be in use
-    if (err != hipSuccess) return err;
-    if (co.mem) hipFree(co.mem);
-    co.mem = nullptr;
     co.n_cap = 0;
-    err = hipMalloc((void**)&co.mem, bytes);
+    hipError_t err = co.dev.reserve(bytes);  // (laid out again whether it grew or not: the capacity changed)
     if (err != hipSuccess) return err;
-    neb::co_ws_layout(nc, cub, co.mem, &co.ws);
+    neb::co_ws_layout(nc, cub, co.dev.mem(), &co.ws);
     co.n_cap = nc;
     return hipSuccess;
 }
@@ -2049,11 +1946,10 @@ NEB_API int neb_rx_coalesce_batch(neb_engine* e, const neb_plain_packet* d_plain
     std::lock_guard<std::mutex> g(e->co.mu);
     CoSpace& co = e->co;
     HIP_TRY(co_reserve(e, n));
-    if (!co.last.same(s)) HIP_TRY(hipStreamWaitEvent(s, co.done, 0));
+    HIP_TRY(co.dev.begin(s));
     HIP_TRY(neb_co_run(d_plain, n, d_in, d_out, out_cap, d_writes, max_writes, d_nwrites, d_pkt_write, d_pkt_status,
                        lanes, hb < 0 ? 0u : hb > 32 ? 32u : (uint32_t)hb, &co.ws, s));
-    HIP_TRY(hipEventRecord(co.done, s));
-    co.last.set(s);
+    HIP_TRY(co.dev.end(s));
     return NEB_OK;
 }
 

@@ -6,18 +6,9 @@
 #include <new>
 #include <vector>
 
+#include "engine_internal.hpp"
 #include "hip_guard.hpp"
 #include "queue_core.hpp"
-
-extern "C" {  // engine.cpp, internal
-void* neb_sched_space_new();
-void neb_sched_space_free(void* p);
-int neb_launch_on(neb_engine* e, int alg, int open, const neb_desc* desc, uint32_t n, uint8_t* arena,
-                  int32_t* status, uint32_t key_hint, hipStream_t s, void* sched);
-int neb_key_alg(neb_engine* e, uint32_t key);
-int neb_engine_device_of(const neb_engine* e);
-bool neb_host_mapped(const void* p);
-}
 
 namespace {
 
@@ -31,7 +22,7 @@ struct HipDev {
     neb_engine* e = nullptr;
     int alg = 0, open = 0;
     std::vector<hipStream_t> stream;
-    std::vector<void*> sched;
+    std::vector<SchedSpace*> sched;
     int launch(uint32_t i, neb_desc* desc, uint32_t n, uint8_t* arena, int32_t* status, uint32_t hint, Token& tok) {
         tok = i;
         return neb_launch_on(e, alg, open, desc, n, arena, status, hint, stream[i], sched[i]);
@@ -96,7 +87,7 @@ NEB_API int neb_queue_destroy(neb_queue* q) {
         if (x.desc) hipHostFree(x.desc);
         if (x.status) hipHostFree(x.status);
     }
-    for (void* sp : q->dev.sched) neb_sched_space_free(sp);
+    for (SchedSpace* sp : q->dev.sched) neb_sched_space_free(sp);
     for (hipStream_t st : q->dev.stream)
         if (st) hipStreamDestroy(st);
     delete q;

@@ -40,29 +40,7 @@
 #include "relay.hpp"
 #include "hip_guard.hpp"
 #include "window_core.hpp"
-
-// engine.cpp
-extern "C" {  // internal (hidden), defined inside engine.cpp's extern "C" block
-bool neb_rx_pipe_begin(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena, uint32_t n, uint32_t nchunks,
-                       neb_desc** h_desc, int32_t** h_status, int* rc);
-int neb_rx_pipe_submit(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena, uint32_t c0, uint32_t cnt,
-                       uint32_t k);
-int neb_rx_pipe_wait(neb_engine* e, uint32_t k);
-void neb_rx_pipe_end(neb_engine* e);
-int neb_engine_device_of(const neb_engine* e);
-int neb_check_batch_args(neb_engine* e, int alg, uint32_t key_hint);
-int neb_open_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
-                         uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s, const uint8_t* rx,
-                         void* prebinned);
-int neb_seal_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
-                         uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s);
-void neb_engine_key_table(const neb_engine* e, const uint32_t** d_keys, uint32_t* max_keys);
-int neb_key_alg(neb_engine* e, uint32_t key);
-void* neb_sched_space_new();
-void neb_sched_space_free(void* p);
-int neb_rx_sched_begin(neb_engine* e, uint32_t n, void* sched, hipStream_t s, neb::SchedWs* ws, uint32_t* max_keys);
-void neb_rx_sched_abort(void* sched);
-}
+#include "engine_internal.hpp"
 
 using namespace neb_rx;
 
@@ -375,6 +353,8 @@ struct neb_dwindows {
     neb::RxDevWin win{};
     uint8_t* mem = nullptr;
     std::mutex mu;  // one receive batch at a time on a window set
+    // ws_mem and wire_mem need no event (workspace.hpp): the receive ends every batch with its stream
+    // synchronized, so nothing is in flight in them when the next batch, on any stream, takes d->mu
     uint8_t* ws_mem = nullptr;
     size_t ws_bytes = 0;
     neb::RxDevWs ws{};
@@ -383,14 +363,12 @@ struct neb_dwindows {
     uint8_t* wire_mem = nullptr;  // neb_rx_open_wire_batch: descriptors + gate statuses
     uint32_t wire_n = 0;
     uint32_t spin_limit = neb::kRxSpinLimit;  // neb_dwindows_set_spin_limit
-    void* sched = nullptr;  // mixed-key AES-GCM receives: the open's scheduler workspace (rxwin.hpp RxBin)
-    // neb_relay_forward_batch: the forward half's workspace (relay.hpp), the event after its last
-    // use and that use's stream, one pinned word for the single target tunnel's key
-    uint8_t* relay_mem = nullptr;
+    SchedSpace* sched = nullptr;  // mixed-key AES-GCM receives: the open's scheduler workspace (rxwin.hpp RxBin)
+    // neb_relay_forward_batch: the forward half's workspace (relay.hpp), which runs on after the
+    // call returns, and one pinned word for the single target tunnel's key
+    neb::HipWorkspace<> relay;
     neb::RelayWs relay_ws{};
     uint32_t relay_n = 0, relay_tun = 0;
-    hipEvent_t relay_done = nullptr;
-    hipStream_t relay_last = nullptr;
     uint32_t* relay_key = nullptr;
 };
 
@@ -490,12 +468,8 @@ NEB_API int neb_dwindows_destroy(neb_dwindows* d) {
         // neb_rx_open_batch returns only once its stream has run the batch, and holds d->mu
         // throughout: with the lock taken, nothing of this window set is in flight
         std::lock_guard<std::mutex> g(d->mu);
-        if (d->sched) neb_sched_space_free(d->sched);
-        if (d->relay_done) {  // the forward half of the last relay batch may still be running
-            hipEventSynchronize(d->relay_done);
-            hipEventDestroy(d->relay_done);
-        }
-        if (d->relay_mem) hipFree(d->relay_mem);
+        neb_sched_space_free(d->sched);
+        d->relay.destroy();  // (waits: the forward half of the last relay batch may still be running)
         if (d->relay_key) hipHostFree(d->relay_key);
         if (d->ws_mem) hipFree(d->ws_mem);
         if (d->wire_mem) hipFree(d->wire_mem);
@@ -597,7 +571,7 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
     // 0. mixed-key AES-GCM: the open's binning (sched_body.hpp) reads only the descriptors, so extra
     //    workgroups of the plan's own launches run it (rxwin.hpp RxBin): three launches off the chain.
     //    A batch large enough for sub-bins is binned by the open itself.
-    void* prebinned = nullptr;
+    SchedSpace* prebinned = nullptr;
     neb::RxBin bin{};
     if (alg == NEB_ALG_AESGCM && key_hint == NEB_KEYS_MIXED && (int64_t)n < neb::knob(NEB_KNOB_SUB_BINS_FROM)) {
         if (!d->sched && !(d->sched = neb_sched_space_new())) return NEB_ERR_HIP;
@@ -833,25 +807,16 @@ static int rx_open_wire_locked(neb_engine* e, int alg, neb_dwindows* d, const ne
     return NEB_OK;
 }
 
-// The forward half's workspace, grown as the receive's is (no allocation in the steady state); a
-// batch on another stream waits for the last one's use of it.
-static int relay_reserve(neb_dwindows* d, uint32_t n, uint32_t ntun, hipStream_t s) {
-    if (!d->relay_done)
-        RX_HIP(hipEventCreateWithFlags(&d->relay_done, hipEventDisableTiming | hipEventDisableSystemFence));
+// The forward half's workspace, grown as the receive's is (no allocation in the steady state).
+static int relay_reserve(neb_dwindows* d, uint32_t n, uint32_t ntun) {
     if (!d->relay_key) RX_HIP(hipHostMalloc((void**)&d->relay_key, sizeof(uint32_t), hipHostMallocDefault));
-    if (d->relay_mem && n <= d->relay_n && ntun <= d->relay_tun) {
-        if (d->relay_last != s) RX_HIP(hipStreamWaitEvent(s, d->relay_done, 0));
-        return NEB_OK;
-    }
+    if (d->relay.mem() && n <= d->relay_n && ntun <= d->relay_tun) return NEB_OK;
     const uint32_t nc = std::max({n, d->relay_n, 1024u}), tc = std::max({ntun, d->relay_tun, 64u});
     size_t cub = 0;
     const size_t bytes = neb_relay_ws_bytes(nc, tc, &cub);
-    RX_HIP(hipEventSynchronize(d->relay_done));  // the old workspace may still be in use
-    if (d->relay_mem) hipFree(d->relay_mem);
-    d->relay_mem = nullptr;
     d->relay_n = d->relay_tun = 0;
-    RX_HIP(hipMalloc((void**)&d->relay_mem, bytes));
-    neb::relay_ws_layout(nc, tc, cub, d->relay_mem, &d->relay_ws);
+    RX_HIP(d->relay.reserve(bytes));  // (laid out again whether it grew or not: the capacities changed)
+    neb::relay_ws_layout(nc, tc, cub, d->relay.mem(), &d->relay_ws);
     d->relay_n = nc;
     d->relay_tun = tc;
     return NEB_OK;
@@ -885,7 +850,8 @@ NEB_API int neb_relay_forward_batch(neb_engine* e, int alg, neb_dwindows* d, con
     std::lock_guard<std::mutex> g(d->mu);
     DeviceGuard dg(neb_engine_device_of(e));
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = relay_reserve(d, n, ntunnels, s)) != NEB_OK) return rc;
+    if ((rc = relay_reserve(d, n, ntunnels)) != NEB_OK) return rc;
+    RX_HIP(d->relay.begin(s));  // after the last batch's forward half, if that ran on another stream
     // one target tunnel: its key, for the single-key seal (read back while the receive runs, which
     // ends with the stream synchronized)
     *d->relay_key = NEB_KEYS_MIXED;
@@ -901,8 +867,7 @@ NEB_API int neb_relay_forward_batch(neb_engine* e, int alg, neb_dwindows* d, con
                           &ws, s));
     rc = neb_seal_batch_count(e, alg, ws.sub_desc, n, ws.nsub, d_arena, ws.sub_status, seal_hint, s);
     if (rc == NEB_OK && neb_relay_fix(&ws, n, d_fwd_status, s) != hipSuccess) rc = NEB_ERR_HIP;
-    (void)hipEventRecord(d->relay_done, s);
-    d->relay_last = s;
+    (void)d->relay.end(s);
     return rc;
 }
 

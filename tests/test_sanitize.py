@@ -1,7 +1,8 @@
 """CPU: the engine's host logic under sanitizers — `make -C nebula_amd sanitize`
 builds window_core.hpp (replay window, exact receive rounds, thread pool) and queue_core.hpp (the
-submission queue, on a CPU device running the oracle) with ASan+UBSan and with TSan and runs them;
-each test also checks its results against the packet-by-packet receive / the oracle."""
+submission queue, on a CPU device running the oracle) and workspace.hpp (the device workspaces'
+event and stream protocol, on a fake device that logs the calls) with ASan+UBSan and with TSan and
+runs them; the first two also check their results against the packet-by-packet receive / the oracle."""
 import os
 import shutil
 import subprocess
@@ -17,3 +18,4 @@ def test_sanitizer_builds_run_clean():
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert r.stdout.count("window_test: ok") == 2 and r.stdout.count("queue_test: ok") == 2, r.stdout
+    assert r.stdout.count("workspace_test: ok") == 2, r.stdout
