@@ -156,12 +156,9 @@ __device__ __forceinline__ uint2 ttab_entry(uint32_t i) {  // i = x*32 + c
 // Wave priority while a round's 16 lookups are issued (s_setprio): the SIMD arbiter then prefers
 // the wave that feeds the LDS over waves busy with their XOR phase, which keeps the LDS queue
 // full. Measured on C2: 0.150 -> 0.136 ms per seal launch (priority 1, 2 and 3 alike; raising it
-// for the GHASH lookups as well was slower). NEB_PRIO=0 disables it.
+// for the GHASH lookups as well was slower).
 #ifndef NEB_PRIO
 #define NEB_PRIO 3
-#endif
-#ifndef NEB_PRIO_AGE  // gcm_single_kernel: the younger half of each SIMD's waves at 1 between lookups
-#define NEB_PRIO_AGE 1
 #endif
 
 struct RkRegs {  // wave-uniform round keys (scalar registers)
@@ -258,18 +255,14 @@ __device__ __forceinline__ uint4 aes256_rounds(uint32_t s0, uint32_t s1, uint32_
 #pragma unroll
     for (int r = FIRST; r < 14; r++) {
         k = rk.get(r);
-#if NEB_PRIO
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(RK::kPrioHi);
-#endif
         const uint32_t a0 = T.t0(s0, 0), a1 = T.t1r(s1, 1), a2 = T.t2(s2, 2), a3 = T.t3r(s3, 3);
         const uint32_t b0 = T.t0(s1, 0), b1 = T.t1r(s2, 1), b2 = T.t2(s3, 2), b3 = T.t3r(s0, 3);
         const uint32_t c0 = T.t0(s2, 0), c1 = T.t1r(s3, 1), c2 = T.t2(s0, 2), c3 = T.t3r(s1, 3);
         const uint32_t d0 = T.t0(s3, 0), d1 = T.t1r(s0, 1), d2 = T.t2(s1, 2), d3 = T.t3r(s2, 3);
-#if NEB_PRIO
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(RK::kPrioLo);
-#endif
         // T0[a] ^ T1[b] ^ T2[c] ^ T3[d] ^ k; with two tables T1 = rotl8 T0, T3 = rotl8 T2
         if constexpr (TL::kFour) {
             if constexpr (RK::kUniform) {
@@ -297,18 +290,14 @@ __device__ __forceinline__ uint4 aes256_rounds(uint32_t s0, uint32_t s1, uint32_
     }
     k = rk.get(14);
     // last round: SubBytes+ShiftRows; S[x] is byte 1 of T0[x]
-#if NEB_PRIO
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(RK::kPrioHi);
-#endif
     const uint32_t a0 = T.t0(s0, 0), a1 = T.t0(s1, 1), a2 = T.t0(s2, 2), a3 = T.t0(s3, 3);
     const uint32_t b0 = T.t0(s1, 0), b1 = T.t0(s2, 1), b2 = T.t0(s3, 2), b3 = T.t0(s0, 3);
     const uint32_t c0 = T.t0(s2, 0), c1 = T.t0(s3, 1), c2 = T.t0(s0, 2), c3 = T.t0(s1, 3);
     const uint32_t d0 = T.t0(s3, 0), d1 = T.t0(s0, 1), d2 = T.t0(s1, 2), d3 = T.t0(s2, 3);
-#if NEB_PRIO
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(RK::kPrioLo);
-#endif
     uint4 o;
     if constexpr (RK::kUniform) {
         o.x = x3s(perm(a1, a0, 0x0C0C0501u), perm(a3, a2, 0x05010C0Cu), k.x);
@@ -461,33 +450,7 @@ __device__ __forceinline__ uint32_t byte_hi_nibble(uint32_t w) {
     return r;
 }
 
-// x · F where ftab (LDS) is a full table F_p[v] at byte p*256 + v*16; acc is XORed in.
-// Table addresses: the high nibble of byte k as is, the low nibble after one shift of the word:
-// 9 VALU per word for its 8 lookups.
-__device__ __forceinline__ uint4 gf_mul_full(uint4 x, uint4 acc, const uint4* ftab) {
-    const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t hi = xw[q];        // byte k: nibble r = 6-2k in bits 4-7
-        const uint32_t lo = xw[q] << 4;   // byte k: nibble r = 7-2k in bits 4-7
-        const uint32_t ah[4] = {byte_hi_nibble<0>(hi), byte_hi_nibble<1>(hi), byte_hi_nibble<2>(hi),
-                                byte_hi_nibble<3>(hi)};
-        const uint32_t al[4] = {byte_hi_nibble<0>(lo), byte_hi_nibble<1>(lo), byte_hi_nibble<2>(lo),
-                                byte_hi_nibble<3>(lo)};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint4 e1 = lds_at<uint4>(ftab, (uint32_t)(8 * q + 6 - 2 * k) * 256u + ah[k]);
-            const uint4 e2 = lds_at<uint4>(ftab, (uint32_t)(8 * q + 7 - 2 * k) * 256u + al[k]);
-            acc = x34(acc, e1, e2);
-        }
-    }
-    return acc;
-}
-
-// The single-key kernel's Horner multiply on 5-bit windows (NEB_GHASH5=0: the nibble table above).
-#ifndef NEB_GHASH5
-#define NEB_GHASH5 1
-#endif
+// The single-key kernel's Horner multiply on 5-bit windows.
 // 26 windows cover x^0..x^127 (128 = 25·5 + 3): window P holds the coefficients x^(5P)..x^(5P+4),
 // its value v has MSB = x^(5P); window 25 has three coefficients, in the top bits of its value.
 constexpr int kWin5 = 26;
@@ -495,7 +458,7 @@ constexpr int kWin5 = 26;
 // 0-1 of position P at byte 2P*256 + 8v, words 2-3 at (2P+1)*256 + 8v. A table is one 256-byte row
 // of the LDS, so the 32 lanes of a ds_read_b64 pass read it conflict-free whatever their entries
 // (distinct entries are distinct bank pairs, equal entries one address), and no lane rotation is
-// needed. 52 ds_read_b64 at 2 array cycles against gf_mul_full's 32 ds_read_b128 at 4.
+// needed. 52 ds_read_b64 at 2 array cycles against the nibble table's 32 ds_read_b128 at 4.
 // One address (v << 3) per window serves both halves; windows 6, 12 and 19 straddle two words.
 __device__ __forceinline__ uint4 gf_mul_full5(uint4 x, uint4 acc, const uint2* f5) {
     const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
@@ -510,7 +473,7 @@ __device__ __forceinline__ uint4 gf_mul_full5(uint4 x, uint4 acc, const uint2* f
         hi[P] = lds_b64(f5, (uint32_t)(2 * P + 1) * 256u + a);
     };
     // The volatile reads keep their program order, so the schedule is written out: the 8 reads of
-    // 4 windows, then their fold; the other waves cover the latency, as in gf_mul_full (2 reads,
+    // 4 windows, then their fold; the other waves cover the latency, as with the nibble table (2 reads,
     // then their fold). C2 A/B over 5 rounds: steps of 2, 4 and 6 windows gave 840.7, 847.8 and
     // 846.6 GiB/s against the nibble table's 814.8 (profiles/ghash5/ab_c2.jsonl); issuing the next
     // step's reads before the fold gained nothing, and from 4 windows ahead on it spills.
@@ -869,54 +832,28 @@ __device__ __forceinline__ uint4 final_perm(uint4 A, const FinalPermLanes& fp, M
 // One key per batch, LPP 4 (gcm_single_kernel): reduction-free full table of H^4 for the Horner
 // step, position tables of H, H^2, H^3, H^4 for the permuted final.
 struct GhFullPerm {
-#if NEB_GHASH5
     const uint2* full;  // F5, the 5-bit window table of H^4 (gf_mul_full5)
-#else
-    const uint4* full;
-#endif
     const void* base;  // the LDS base of FinalPermLanes::off
     FinalPermLanes fp;
     __device__ __forceinline__ uint4 horner(uint4 a, uint32_t) const {
-#if NEB_GHASH5
         return gf_mul_full5(a, make_uint4(0, 0, 0, 0), full);
-#else
-        return gf_mul_full(a, make_uint4(0, 0, 0, 0), full);
-#endif
     }
     __device__ __forceinline__ uint4 final(uint4 A, uint32_t, uint32_t) const {
         return final_perm(A, fp, [&](uint4 a, uint32_t off) { return gf_mul_pos_off(a, base, off); });
     }
 };
 
-// Pairwise tree over the packet's lanes: level i folds V_l·H^(2^i) ⊕ V_(l+2^i) into the lanes
-// l ≡ 0 mod 2^(i+1); after lg levels lane 0 holds Z with Σ_l A_l·H^(LPP-l) = Z·H: lg + 1 multiplies
-// instead of a Horner's LPP. shoup_off(i): LDS byte offset (from base) of the Shoup table of H^(2^i).
-template <class OFF>
-__device__ __forceinline__ uint4 tree_final(uint4 A, uint32_t lane, uint32_t lg, const uint4* base, OFF&& shoup_off) {
-    uint4 V = A;
-    for (uint32_t i = 0; i < lg; i++) V = xor4(gf_mul_shoup(V, shoup_off(i), base), shfl_down4(V, 1u << i));
-    V = gf_mul_shoup(V, shoup_off(0u), base);
-    return shfl4(V, lane & ~((1u << lg) - 1u));
-}
-
 // 64 lanes per packet (the tail and per-packet kernels): lane l = 16a + b needs A_l·H^(64-l) =
 // A_l·H^(16-b)·H^(16(3-a)). Each lane multiplies by its own M_(16-b) (the record's Shoup tables
 // of H^1..H^16, m16), the 16 lanes of a quarter XOR their products (S_a), quarters 0 and 2 multiply
 // by H^16 and then quarters 0 and 1 by H^32, and the quarters XOR: 3 dependent multiplies instead
-// of the tree's 7 (GhShoup, kept for other lane counts). NEB_TAIL_TREE=1 keeps the tree (A/B).
-#ifndef NEB_TAIL_TREE
-#define NEB_TAIL_TREE 0
-#endif
+// of a pairwise tree's 7.
 struct GhShoup64 {
     const uint4* m16;    // M_1..M_16, 256 B each
-    const uint4* shoup;  // M of H^(2^j), j < 6: M_32 is j = 5 (the tree of the A/B build)
     const uint4* pos;    // position tables of H^64 (the Horner stride)
     const uint4* hi;     // M_16, M_32, M_48: the quarters' powers
     __device__ __forceinline__ uint4 horner(uint4 a, uint32_t) const { return gf_mul_pos(a, pos); }
     __device__ __forceinline__ uint4 final(uint4 A, uint32_t lane, uint32_t lg) const {
-#if NEB_TAIL_TREE
-        return tree_final(A, lane, lg, shoup, [](uint32_t i) { return i * 256u; });
-#else
         const uint32_t b = lane & 15u, a = (lane >> 4) & 3u;
         uint4 V = gf_mul_shoup(A, (15u - b) * 256u, m16);
         V = xor4(V, shfl_xor4(V, 8));
@@ -927,7 +864,6 @@ struct GhShoup64 {
         V = a < 3u ? W : V;
         V = xor4(V, shfl_xor4(V, 16));
         return xor4(V, shfl_xor4(V, 32));
-#endif
     }
 };
 
@@ -1249,17 +1185,11 @@ constexpr int kSingleWpe = 4;  // launch bound: waves per SIMD
 constexpr int kSingleThreads = kSingleWaves * kWave;
 
 struct SingleLds {
-#if NEB_GHASH5
     uint2 full[2 * kWin5 * 32];  // 13 KiB  F5[P][v] for H^4, halves (first: its offsets fit the ds_read offset field)
-#else
-    uint4 full[32 * 16];       // 8 KiB   F_p[v] for H^4 (first: its offsets fit the ds_read offset field)
-#endif
     uint4 pos1[8 * 16];        // 2 KiB   position tables of H
     uint2 ttab[2 * 256 * 32];  // 128 KiB (T0,T1) and (T2,T3) pairs, 32 copies each
     uint4 pos23[2][8 * 16];    // 4 KiB   position tables of H^2 and H^3 (the permuted final)
-#if NEB_GHASH5
     uint4 pos4[8 * 16];        // 2 KiB   position tables of H^4 (the final's; positions 0-7 of the nibble table)
-#endif
 };
 struct SingleLdsCs : SingleLds {
     uint4 pow2[10 * 16];  // 2.5 KiB  Shoup tables of H^(2^j), j < 10 (the TX checksum correction)
@@ -1279,7 +1209,6 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
     // the record's GHASH tables: loaded before the T-table fill and stored after it, so their
     // latency overlaps the fill's instead of following it
     uint4 r_full = make_uint4(0, 0, 0, 0), r_h = make_uint4(0, 0, 0, 0), r_p = make_uint4(0, 0, 0, 0);
-#if NEB_GHASH5
     // F5[P][v] from the record's nibble table: x^b·H^4 is its entry F_(b/4)[8 >> (b%4)], and thread
     // t < 26·32 XORs those of the (at most five) coefficients x^(5P+j) that v = t mod 32 selects
     static_assert(kSingleThreads >= kWin5 * 32, "one window-table entry per thread");
@@ -1295,23 +1224,13 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
     }
     if (tid < 128u) r_h = ld_rec4(srec, kRecPos1 + 4u * tid);
     if (tid < 384u) r_p = ld_rec4(srec, (tid < 128u ? kRecPos2 : tid < 256u ? kRecPos3 : kRecFull) + 4u * (tid & 127u));
-#else
-    static_assert(kSingleThreads >= 512, "one full-table entry per thread");
-    if (tid < 512u) r_full = ld_rec4(srec, kRecFull + 4u * tid);
-    if (tid < 128u) r_h = ld_rec4(srec, kRecPos1 + 4u * tid);
-    if (tid < 256u) r_p = ld_rec4(srec, (tid < 128u ? kRecPos2 : kRecPos3) + 4u * (tid & 127u));
-#endif
     const TLook4 T{lds.ttab, ttab4_lane_base(lane)};
     fill_ttab<2u * 256u * 32u, kSingleThreads>(lds.ttab, tid, ttab4_entry);
-#if NEB_GHASH5
     if (tid < (uint32_t)kWin5 * 32u) {
         lds.full[(2u * f5_p) * 32u + f5_v] = make_uint2(r_full.x, r_full.y);
         lds.full[(2u * f5_p + 1u) * 32u + f5_v] = make_uint2(r_full.z, r_full.w);
     }
     if (tid >= 256u && tid < 384u) lds.pos4[tid & 127u] = r_p;
-#else
-    if (tid < 512u) lds.full[tid] = r_full;
-#endif
     if (tid < 128u) lds.pos1[tid] = r_h;
     if (tid < 256u) lds.pos23[tid >> 7][tid & 127u] = r_p;
 
@@ -1324,11 +1243,7 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
     load_round_keys(srec, rks);
     __syncthreads();
     const RkRegs rk{rks};
-#if NEB_GHASH5
     const uint32_t tab_off[4] = {(uint32_t)offsetof(SingleLds, pos4), (uint32_t)offsetof(SingleLds, pos23[1]),
-#else
-    const uint32_t tab_off[4] = {(uint32_t)offsetof(SingleLds, full), (uint32_t)offsetof(SingleLds, pos23[1]),
-#endif
                                  (uint32_t)offsetof(SingleLds, pos23[0]), (uint32_t)offsetof(SingleLds, pos1)};
     const GhFullPerm gh{lds.full, &lds, final_perm_lanes(lane, tab_off)};
 
@@ -1362,7 +1277,6 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
 #endif
         }
     };
-#if NEB_PRIO && NEB_PRIO_AGE
     // A workgroup's waves w, w+4, w+8, w+12 share a SIMD in that age order (wave >> 2 is the
     // rank), and the SIMD arbiter serves the older first at equal priority: ranks 0-3 finished
     // their groups in 74 / 78 / 84 / 88 µs (tools/wave_trace.py, C2 seal, settled clock). Ranks 2
@@ -1372,9 +1286,6 @@ __global__ __launch_bounds__(kSingleThreads, kSingleWpe) void gcm_single_kernel(
     // rank, four distinct levels, 0/1/1/1, 0/0/2/2 — was equal or slower.
     if (__builtin_amdgcn_readfirstlane(wave) >> 3) groups(RkRegsPrio<NEB_PRIO, 1>{rk});
     else groups(rk);
-#else
-    groups(rk);
-#endif
 }
 
 // The tail pass: the packets after gcm_single_kernel's full passes over args.tail_slots waves (the
@@ -1395,7 +1306,7 @@ constexpr uint32_t kSmallBatch = 6144;
 constexpr int kTailWaves = 8;
 struct TailLds {
     uint2 ttab[256 * 32];       // 64 KiB T-table pairs, 32 copies
-    uint4 shoup[kTailLg * 16];  // 1.5 KiB
+    uint4 shoup[kTailLg * 16];  // 1.5 KiB: M of H^(2^j), still staged; only the removed tree final read it
     uint4 pos[8 * 16];          // 2 KiB
     uint4 m16[16 * 16];         // 4 KiB: M_1..M_16 (GhShoup64)
     uint4 hi[3 * 16];           // M_16, M_32, M_48 (GhShoup64)
@@ -1428,7 +1339,7 @@ __global__ __launch_bounds__(kTailWaves * kWave) void gcm_single_tail_kernel(Gcm
     load_round_keys(srec, rks);
     __syncthreads();
     const TLook T{lds.ttab, ttab_lane_base(lane)};
-    const GhShoup64 gh{lds.m16, lds.shoup, lds.pos, lds.hi};
+    const GhShoup64 gh{lds.m16, lds.pos, lds.hi};
     const bool key_ok = __builtin_amdgcn_readfirstlane(srec[kRecAlg]) == NEB_ALG_AESGCM;
     for (uint32_t t = blockIdx.x * kTailWaves + wave; t < tgroups; t += gridDim.x * kTailWaves) {
         const uint32_t p = p0 + kTailPpw * t + (lane >> kTailLg);
@@ -1506,7 +1417,7 @@ __global__ __launch_bounds__(kOneFillThreads) void gcm_one_kernel(OneArgs a) {
     uint32_t rks[60];
     load_round_keys(srec, rks);
     const TLook T{lds.ttab, ttab_lane_base(lane)};
-    const GhShoup64 gh{lds.m16, lds.shoup, lds.pos, lds.hi};
+    const GhShoup64 gh{lds.m16, lds.pos, lds.hi};
     const bool key_ok = key < a.max_keys && __builtin_amdgcn_readfirstlane(srec[kRecAlg]) == NEB_ALG_AESGCM;
     uint8_t* base = const_cast<uint8_t*>(ka + offsetof(OneArgs, in));
     __shared__ int32_t s_status;
@@ -1596,7 +1507,7 @@ __global__ __launch_bounds__(kOneBatchWaves * kWave) void gcm_one_batch_kernel(c
     uint32_t rks[60];
     load_round_keys(srec, rks);
     const TLook T{lds.ttab, ttab_lane_base(lane)};
-    const GhShoup64 gh{kt.m16, kt.shoup, kt.pos, kt.hi};
+    const GhShoup64 gh{kt.m16, kt.pos, kt.hi};
     const bool key_ok = key < max_keys && __builtin_amdgcn_readfirstlane(srec[kRecAlg]) == NEB_ALG_AESGCM;
     // the bytes in LDS, addressed through a generic pointer (flat loads): the descriptor's offsets are
     // from the slots' base, so the LDS copy stands at slot r's place; the output goes to the slot in
@@ -1723,7 +1634,6 @@ __global__ __launch_bounds__(kChunkThreads, kChunkWpe) void gcm_chunk_kernel(Gcm
     c = __builtin_amdgcn_readfirstlane(c);
     uint4 ch_next = make_uint4(0, 0, 0, 0);
     if (c < nch) ch_next = chunk_at(c);
-#if NEB_CHUNK_STEAL
 #ifndef NEB_STEAL_MIN_PER_WG
 #define NEB_STEAL_MIN_PER_WG 32u
 #endif
@@ -1747,13 +1657,6 @@ __global__ __launch_bounds__(kChunkThreads, kChunkWpe) void gcm_chunk_kernel(Gcm
         }
         return __builtin_amdgcn_readfirstlane(k);
     };
-#else
-    auto claim = [&]() -> uint32_t {
-        uint32_t k = 0;
-        if (lane == 0u) k = chunk_of(atomicAdd(&wg_cursor, 1u));
-        return __builtin_amdgcn_readfirstlane(k);
-    };
-#endif
     while (c < nch) {
         const uint4 ch = ch_next;
         NEB_MARK(chunk_begin);
@@ -2259,39 +2162,7 @@ __global__ __launch_bounds__(256) void copy_desc_kernel(uint4* __restrict__ dst,
                                                         uint32_t nvec) {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nvec; i += gridDim.x * 256u) dst[i] = src[i];
 }
-// A host-staged chunk's span between pinned host memory and HBM (engine.cpp batch_host,
-// NEB_PIPE_COPY): 16-byte vectors (both ends share their address mod 16), four in flight per lane,
-// bytes at the ragged ends.
-__global__ __launch_bounds__(256) void copy_span_kernel(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src,
-                                                        size_t head, size_t nvec, size_t bytes) {
-    const size_t tid = (size_t)blockIdx.x * 256u + threadIdx.x, nthr = (size_t)gridDim.x * 256u;
-    uint4* d = reinterpret_cast<uint4*>(dst + head);
-    const uint4* s = reinterpret_cast<const uint4*>(src + head);
-    size_t i = tid;
-    for (; i + 3u * nthr < nvec; i += 4u * nthr) {
-        const uint4 a = s[i], b = s[i + nthr], c = s[i + 2u * nthr], e = s[i + 3u * nthr];
-        d[i] = a;
-        d[i + nthr] = b;
-        d[i + 2u * nthr] = c;
-        d[i + 3u * nthr] = e;
-    }
-    for (; i < nvec; i += nthr) d[i] = s[i];
-    for (size_t j = tid; j < head; j += nthr) dst[j] = src[j];
-    for (size_t j = head + nvec * 16u + tid; j < bytes; j += nthr) dst[j] = src[j];
-}
 }  // namespace neb
-
-extern "C" hipError_t neb_copy_span(void* dst, const void* src, size_t bytes, hipStream_t s) {
-    if (!bytes) return hipSuccess;
-    auto* d = static_cast<uint8_t*>(dst);
-    auto* src8 = static_cast<const uint8_t*>(src);
-    if (((uintptr_t)d & 15u) != ((uintptr_t)src8 & 15u)) return hipErrorInvalidValue;  // (the caller copies)
-    const size_t head = std::min(bytes, (size_t)((16u - ((uintptr_t)d & 15u)) & 15u));
-    const size_t nvec = (bytes - head) / 16u;
-    const uint32_t grid = (uint32_t)std::min<size_t>((nvec + 255u) / 256u, 2048u);
-    hipLaunchKernelGGL(neb::copy_span_kernel, dim3(std::max(grid, 1u)), dim3(256), 0, s, d, src8, head, nvec, bytes);
-    return hipGetLastError();
-}
 
 extern "C" hipError_t neb_copy_desc(neb_desc* dst, const neb_desc* src, uint32_t n, hipStream_t s) {
     static_assert(sizeof(neb_desc) % 16 == 0, "descriptors copy as 16-byte vectors");

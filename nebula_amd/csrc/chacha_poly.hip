@@ -78,10 +78,6 @@ __device__ __forceinline__ uint4 chacha_quad(uint32_t a0, uint32_t b0, uint32_t 
     c = dpp_add<P2>(c, d); b = rotl(dpp_xor<P1>(b, c), 12);                              \
     a += b; d ^= a; d = rotl(d, 8);                                                     \
     c += d; b ^= c; b = rotl(b, 7);
-#ifndef NEB_CHACHA_DPP
-#define NEB_CHACHA_DPP 1
-#endif
-#if NEB_CHACHA_DPP
     constexpr int kL1 = 0x39, kL2 = 0x4E, kL3 = 0x93;  // quad_perm [1,2,3,0], [2,3,0,1], [3,0,1,2]
     NEB_QR(a, b, c, d)
     NEB_QR_DPP(kL1, kL2, kL3)  // diagonal round: lane w takes b from w+1, c from w+2, d from w+3
@@ -93,19 +89,6 @@ __device__ __forceinline__ uint4 chacha_quad(uint32_t a0, uint32_t b0, uint32_t 
     b = qperm<3, 0, 1, 2>(b);
     c = qperm<2, 3, 0, 1>(c);
     d = qperm<1, 2, 3, 0>(d);
-#else  // separate quad_perm moves before and after each diagonal round
-#pragma unroll 2
-    for (int i = 0; i < 10; i++) {
-        NEB_QR(a, b, c, d)
-        b = qperm<1, 2, 3, 0>(b);
-        c = qperm<2, 3, 0, 1>(c);
-        d = qperm<3, 0, 1, 2>(d);
-        NEB_QR(a, b, c, d)
-        b = qperm<3, 0, 1, 2>(b);
-        c = qperm<2, 3, 0, 1>(c);
-        d = qperm<1, 2, 3, 0>(d);
-    }
-#endif
 #undef NEB_QR_DPP
     a += a0; b += b0; c += c0; d += d0;
     // 4x4 transpose inside the quad: lane w holds row elements (word 4e + w, e = 0..3) and needs

@@ -30,6 +30,7 @@
 #include "knobs.hpp"
 #include "host_common.hpp"
 #include "layout.hpp"
+#include "pipe_core.hpp"
 #include "rxwin.hpp"
 #include "sched.hpp"
 #include "timing.hpp"
@@ -51,7 +52,6 @@ extern "C" hipError_t neb_gcm_batch_single(int open, const neb_desc* d_desc, uin
 extern "C" hipError_t neb_gcm_one(int open, const uint8_t* aad, uint32_t aad_len, const uint8_t* in, uint32_t in_len,
                                   uint32_t len, uint64_t counter, uint8_t* out, int32_t* status, const uint32_t* d_keys,
                                   uint32_t max_keys, uint32_t key, hipStream_t s);
-extern "C" hipError_t neb_copy_span(void* dst, const void* src, size_t bytes, hipStream_t s);
 extern "C" hipError_t neb_copy_desc(neb_desc* dst, const neb_desc* src, uint32_t n, hipStream_t s);
 extern "C" hipError_t neb_gcm_one_batch(int open, const neb_desc* descs, int32_t* status, uint8_t* slots, uint32_t n,
                                         const uint32_t* d_keys, uint32_t max_keys, hipStream_t s);
@@ -66,9 +66,6 @@ extern "C" hipError_t neb_gcm_batch_chunked(int open, const neb_desc* d_desc, ui
                                             const uint8_t* rx);
 extern "C" hipError_t neb_gcm_probe(void);
 extern "C" uint32_t neb_gcm_single_slots(uint32_t n, int cu_count, int open, int hdr_from_dst);
-#ifndef NEB_TX_CSUM_SEAL
-#define NEB_TX_CSUM_SEAL 1  // 0: the segment kernel sums every checksum (A/B)
-#endif
 extern "C" hipError_t neb_chacha_batch(int open, const neb_desc* d_desc, uint32_t n, uint8_t* d_arena,
                                        const uint32_t* d_keys, uint32_t max_keys, uint32_t key_hint,
                                        int32_t* d_status, const uint32_t* d_n, int cu_count, hipStream_t s,
@@ -87,39 +84,8 @@ struct SchedSpace {
 namespace {
 
 constexpr size_t kStageMin = 1 << 16;
-// The staged host pipeline (batch_host, round 6): chunks of kPipeChunkPkts packets through
-// kPipeSlots device buffers, with the copies in, the kernels and the copies back on three streams
-// of their own, chained by events: chunk k + 1's copy-in then runs beside chunk k - 1's copy-back
-// (PCIe carries both directions at once: 56 GB/s each alone, 96 GB/s together on this box).
-// Chunks ramp up from kPipeFirst packets (doubling) to kPipeChunkPkts and back down at the end, so the
-// first copy-in and the last copy-back, which run with nothing beside them, are short. A/B on C2
-// (profiles/r6/host/): chunks of 4096 / 8192 / 12288 / 16384 / 32768 packets 23.9 / 26.6 / 32.6-33.2 /
-// 32.6 / 28.5 GiB/s; a 16384-packet copy-in runs 395 µs alone and 520 µs beside a copy-back (42 + 51
-// GB/s), and the first and last of each call ran alone for ≈ 0.9 of its 2.7 ms.
-constexpr int kPipeSlots = 4;
-#ifndef NEB_PIPE_CHUNK
-#define NEB_PIPE_CHUNK 16384
-#endif
-#ifndef NEB_PIPE_FIRST
-#define NEB_PIPE_FIRST 4096
-#endif
-constexpr uint32_t kPipeChunkPkts = NEB_PIPE_CHUNK;  // packets per staged host chunk at most
-constexpr uint32_t kPipeFirst = NEB_PIPE_FIRST;      // the first and last chunks' packets
-
-// chunk sizes for a batch of n packets: kPipeFirst, 2 kPipeFirst, ... up to kPipeChunkPkts at both
-// ends (while the rest still holds 4x the next size), full chunks between
-std::vector<uint32_t> pipe_plan(uint32_t n) {
-    std::vector<uint32_t> head, plan;
-    uint32_t rem = n;
-    for (uint32_t s = kPipeFirst; s < kPipeChunkPkts && rem >= 4u * s; s *= 2u) {
-        head.push_back(s);
-        rem -= 2u * s;
-    }
-    plan = head;
-    for (; rem; rem -= std::min(rem, kPipeChunkPkts)) plan.push_back(std::min(rem, kPipeChunkPkts));
-    plan.insert(plan.end(), head.rbegin(), head.rend());
-    return plan;
-}
+using neb::kPipeChunkPkts;  // pipe_core.hpp: the staged host pipeline's chunk plan and spans
+using neb::kPipeSlots;
 
 struct PipeSlot {
     uint8_t* d_buf = nullptr;
@@ -129,16 +95,19 @@ struct PipeSlot {
     int32_t* h_status = nullptr; // pinned, mapped: the kernels write it in place
     int32_t* user_status = nullptr;
     uint32_t user_begin = 0, count = 0;
-    uint64_t lo = 0, hi = 0;        // arena span of the chunk in flight (count > 0)
+    neb::PipeSpan span;             // arena span of the chunk in flight (count > 0)
     hipEvent_t in_done = nullptr;   // the chunk's copies in are done (the kernel waits for it)
     hipEvent_t k_done = nullptr;    // its kernel is done (the copies back wait for it)
     hipEvent_t done = nullptr;      // its span and statuses are back (the slot is free)
-    bool back_pending = false;      // statuses taken at k_done; the copy back may still read d_buf
 };
 struct Pipe {
     hipStream_t h2d = nullptr, comp = nullptr, d2h = nullptr;
     PipeSlot slot[kPipeSlots];
     SchedSpace* sched = nullptr;  // the compute stream's mixed-key workspace
+
+    int ensure(neb_engine* e);         // streams, events and slot buffers, created once
+    hipError_t retire(PipeSlot& s);    // wait for the slot's chunk, hand its statuses to the caller
+    void drain();                      // after a failure: nothing queued, no chunk in flight
 };
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -540,17 +509,11 @@ NEB_API int neb_engine_create(int device, uint32_t max_keys, neb_engine** out) {
     // Streams of the default priority share the process's 4 queues, handed out in the order
     // 1 2 3 4 4 3 2 1 (tools/native/queue_map.cpp under rocprofv3): after the null stream and the
     // engine's stream the pool's 4 landed on 2 queues, and 4 threads' calls ran 2 kernels at a time
-    // (round 6 trace, profiles/r6/percall/). NEB_PKT_PRIO=0: default priority (A/B).
-    static const bool prio = [] {
-        const char* v = std::getenv("NEB_PKT_PRIO");
-        return !(v && v[0] == '0');
-    }();
+    // (round 6 trace, profiles/r6/percall/).
     int least = 0, greatest = 0;
-    if (prio) (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
     for (PktSlot& sl : e->pkt.slot) {
-        ok = ok &&
-             (prio ? hipStreamCreateWithPriority(&sl.stream, hipStreamNonBlocking, greatest)
-                   : hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking)) == hipSuccess &&
+        ok = ok && hipStreamCreateWithPriority(&sl.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
              hipHostMalloc((void**)&sl.h, kStageMin, hipHostMallocDefault) == hipSuccess;
         if (ok) {
             sl.cap = kStageMin;
@@ -916,16 +879,6 @@ static uint32_t front_groups(const neb_engine* e, uint32_t n) {
     return below > 0 && cap > 0 && (uint64_t)n < (uint64_t)below * waves ? (uint32_t)std::min<int64_t>(cap, 8) : 8u;
 }
 
-// NEB_BIND_EVENTS=0 (read once): markers after each batch instead of events bound to its last
-// kernel's dispatch (the A/B of round 4's binding for mixed-key AES-GCM and ChaCha batches)
-static bool bind_events() {
-    static const bool on = [] {
-        const char* v = std::getenv("NEB_BIND_EVENTS");
-        return !(v && v[0] == '0');
-    }();
-    return on;
-}
-
 // d_n (optional): the batch's real packet count in device memory, at most n (a batch whose size is
 // only known on the device, e.g. the segments of a TX batch). hdr_from_dst: the TX batch's
 // descriptors (tx.hip) read their first `flags` plaintext bytes from the destination.
@@ -954,11 +907,11 @@ static hipError_t launch_batch(neb_engine* e, int alg, int open, const neb_desc*
         if (err == hipSuccess)  // the workspace's event bound to the chunk kernel's dispatch: no marker packet between batches
             err = neb_gcm_batch_chunked(open, d_desc, n, d_arena, e->d_keys, e->max_keys, d_status, sp.ws.sorted,
                                         sp.ws.chunks, sp.ws.counters, sp.ws.max_chunks, e->cu_count,
-                                        s, hdr_from_dst, bind_events() ? sp.dev.event() : nullptr,
+                                        s, hdr_from_dst, sp.dev.event(),
                                         prebinned ? nullptr : rx);  // (prebinned: refused packets unlisted)
-        if (err == hipSuccess && bind_events()) sp.dev.end_bound(s);
-        else if (err == hipSuccess) err = sp.dev.end(s);
-        if (err != hipSuccess) {
+        if (err == hipSuccess) {
+            sp.dev.end_bound(s);
+        } else {
             // binning passes of this batch may already be queued on s: let them finish before the
             // next batch clears the counters (sched_reserve's dirty path waits on the event only)
             (void)hipStreamSynchronize(s);
@@ -1020,40 +973,34 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
     if (!sl.reserve(total)) return NEB_ERR_HIP;
     uint8_t* h = sl->h;
     // The packet's bytes travel in the kernel's arguments and only the result comes back through
-    // the slot (aes_gcm.hip gcm_one_kernel, chacha_poly.hip chacha_one_kernel); NEB_ONE_KERNEL=0
-    // for the A/B
-    static const bool one = [] {
-        const char* v = std::getenv("NEB_ONE_KERNEL");
-        return !(v && v[0] == '0');
-    }();
-    if (one) {
-        *(int32_t*)(h + o_status) = -1;
-        auto* fn = c->alg == NEB_ALG_AESGCM ? neb_gcm_one : neb_chacha_one;
-        hipError_t err = fn(open, ad, (uint32_t)ad_len, in, (uint32_t)in_len, (uint32_t)pay_len, n, h + o_pay,
-                            (int32_t*)(h + o_status), e->d_keys, e->max_keys, c->key_id, sl->stream);
-        if (err == hipSuccess) {
-            // the kernel publishes the status last, behind a system-scope release of the result
-            // (device_common.hpp one_publish_status): poll it, and wait for the stream only if it
-            // does not come (a fault reports there)
-            int32_t st = -1;
-            if (!poll_status(reinterpret_cast<const int32_t*>(h + o_status), &st)) {
-                err = hipStreamSynchronize(sl->stream);
-                if (err != hipSuccess) {
-                    set_error("one_packet", err);
-                    return NEB_ERR_HIP;
-                }
-                st = __atomic_load_n(reinterpret_cast<const int32_t*>(h + o_status), __ATOMIC_ACQUIRE);
+    // the slot (aes_gcm.hip gcm_one_kernel, chacha_poly.hip chacha_one_kernel).
+    *(int32_t*)(h + o_status) = -1;
+    auto* fn = c->alg == NEB_ALG_AESGCM ? neb_gcm_one : neb_chacha_one;
+    hipError_t err = fn(open, ad, (uint32_t)ad_len, in, (uint32_t)in_len, (uint32_t)pay_len, n, h + o_pay,
+                        (int32_t*)(h + o_status), e->d_keys, e->max_keys, c->key_id, sl->stream);
+    if (err == hipSuccess) {
+        // the kernel publishes the status last, behind a system-scope release of the result
+        // (device_common.hpp one_publish_status): poll it, and wait for the stream only if it
+        // does not come (a fault reports there)
+        int32_t st = -1;
+        if (!poll_status(reinterpret_cast<const int32_t*>(h + o_status), &st)) {
+            err = hipStreamSynchronize(sl->stream);
+            if (err != hipSuccess) {
+                set_error("one_packet", err);
+                return NEB_ERR_HIP;
             }
-            *st_out = st;
-            copy_result(open, st, dst, h + o_pay, pay_len);
-            return NEB_OK;
+            st = __atomic_load_n(reinterpret_cast<const int32_t*>(h + o_status), __ATOMIC_ACQUIRE);
         }
-        if (err != hipErrorInvalidValue) {  // (too large for the arguments: the batch path below)
-            set_error("one_packet", err);
-            return NEB_ERR_HIP;
-        }
-        (void)hipGetLastError();
+        *st_out = st;
+        copy_result(open, st, dst, h + o_pay, pay_len);
+        return NEB_OK;
     }
+    if (err != hipErrorInvalidValue) {
+        set_error("one_packet", err);
+        return NEB_ERR_HIP;
+    }
+    (void)hipGetLastError();
+    // too large for the kernel arguments: one descriptor through the batch path
     neb_desc d{};
     d.src_off = o_pay - o_aad;
     d.dst_off = o_pay - o_aad;
@@ -1066,8 +1013,8 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
     *(int32_t*)(h + o_status) = -1;
     if (ad_len) std::memcpy(h + o_aad, ad, ad_len);
     if (in_len) std::memcpy(h + o_pay, in, in_len);
-    hipError_t err = launch_batch(e, c->alg, open, (const neb_desc*)(h + o_desc), 1, h + o_aad,
-                                  (int32_t*)(h + o_status), c->key_id, sl->stream);
+    err = launch_batch(e, c->alg, open, (const neb_desc*)(h + o_desc), 1, h + o_aad, (int32_t*)(h + o_status),
+                       c->key_id, sl->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(sl->stream);
     if (err != hipSuccess) {
         set_error("one_packet", err);
@@ -1085,12 +1032,8 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
 static int one_packet(neb_cipher* c, int open, const uint8_t* ad, size_t ad_len, const uint8_t* in, size_t in_len,
                       size_t pay_len, uint64_t n, uint8_t* dst, int32_t* st_out) {
     neb_engine* e = c->e;
-    static const bool comb_on = [] {  // NEB_PKT_COMBINE=0: every call alone (A/B)
-        const char* v = std::getenv("NEB_PKT_COMBINE");
-        return !(v && v[0] == '0');
-    }();
     const size_t pay = align_up(ad_len, 16);
-    if (!comb_on || c->alg != NEB_ALG_AESGCM || pay + std::max(in_len, pay_len + 16) > kCombSlot || pay + in_len > 2048)
+    if (c->alg != NEB_ALG_AESGCM || pay + std::max(in_len, pay_len + 16) > kCombSlot || pay + in_len > 2048)
         return one_packet_solo(c, open, ad, ad_len, in, in_len, pay_len, n, dst, st_out);
     static const uint32_t max_inflight = [] {  // NEB_PKT_INFLIGHT: launches in flight (A/B), default 4
         const char* v = std::getenv("NEB_PKT_INFLIGHT");
@@ -1270,8 +1213,7 @@ static int batch_device(neb_engine* e, int alg, int open, const neb_desc* d_desc
     // its chunk kernel the same way and orders every later user of the workspace after it;
     // neb_cipher_destroy waits on that event, so it needs no key-use event of its own.
     const bool sched = alg == NEB_ALG_AESGCM && key_hint == NEB_KEYS_MIXED;
-    const bool single_aes = alg == NEB_ALG_AESGCM && key_hint != NEB_KEYS_MIXED;  // bound since round 3
-    hipEvent_t stop = sched || !(single_aes || bind_events()) ? nullptr : use_event(e, key_hint, s);
+    hipEvent_t stop = sched ? nullptr : use_event(e, key_hint, s);
     hipError_t err = launch_batch(e, alg, open, d_desc, n, d_arena, d_status, key_hint, s, nullptr, nullptr, 0, stop);
     if (err != hipSuccess) {
         set_error("batch launch", err);
@@ -1415,12 +1357,59 @@ static int batch_host_zero_copy(neb_engine* e, int alg, int open, const neb_desc
     return NEB_OK;
 }
 
+// ---- the staged host pipeline (pipe_core.hpp) -------------------------------------------------
+
+// Each of the pipeline's streams on a hardware queue of its own: a stream with a CU mask gets one
+// (all CUs here; tools/native/queue_map.cpp), where default streams share the process's 4 and two
+// of the pipeline's could land on one, so a chunk's kernel queued behind the previous chunk's copy
+// back. Such streams are blocking streams: they and the null stream wait on each other.
+int Pipe::ensure(neb_engine* e) {
+    for (hipStream_t* st : {&h2d, &comp, &d2h}) {
+        if (*st) continue;
+        std::vector<uint32_t> mask(((uint32_t)e->cu_count + 31u) / 32u, 0u);
+        for (int c = 0; c < e->cu_count; c++) mask[c / 32] |= 1u << (c % 32);
+        HIP_TRY(hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()));
+    }
+    if (!sched && !(sched = new (std::nothrow) SchedSpace)) return NEB_ERR_INVALID;
+    for (auto& s : slot) {
+        if (!s.done) {
+            for (hipEvent_t* ev : {&s.in_done, &s.k_done, &s.done})
+                HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+            HIP_TRY(hipHostMalloc((void**)&s.h_desc, kPipeChunkPkts * sizeof(neb_desc), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void**)&s.d_desc, kPipeChunkPkts * sizeof(neb_desc)));
+            HIP_TRY(hipHostMalloc((void**)&s.h_status, kPipeChunkPkts * sizeof(int32_t), hipHostMallocDefault));
+        }
+        s.count = 0;
+    }
+    return NEB_OK;
+}
+
+// The host waits for the chunk's copy back. In the trace each copy-in then starts as the copy back
+// two chunks before it ends, 284 µs per call idle on the copy-in stream (profiles/r6/host/
+// final_*_trace.csv, tools/r6/copy_overlap.py). Two ways of removing that wait measured no better
+// and were removed: waiting for the copy back on the device, 27.9-29.3 against
+// 31.7-33.4 GiB/s (ab_gpu_wait.jsonl); an empty kernel after each copy back with the event after
+// it, 30.5-32.3 against 31.3-32.9 (ab_mark.jsonl).
+hipError_t Pipe::retire(PipeSlot& s) {
+    hipError_t err = hipEventSynchronize(s.done);
+    if (err != hipSuccess) return err;
+    std::memcpy(s.user_status + s.user_begin, s.h_status, s.count * sizeof(int32_t));
+    s.count = 0;
+    return hipSuccess;
+}
+
+void Pipe::drain() {
+    for (hipStream_t st : {h2d, comp, d2h}) (void)hipStreamSynchronize(st);
+    for (auto& s : slot) s.count = 0;
+}
+
 // Host-resident batch. A pinned, mapped arena runs zero-copy (above). Any other arena is staged in
-// chunks of kPipeChunkPkts packets rotated over kPipeStreams streams: each chunk's arena span is
-// copied in (hipMemcpyAsync), sealed/opened on the device and copied back, so one chunk's copy-in
-// overlaps another's kernel and another's copy-back. NEB_HOST_MODE=dma forces the staging for a
-// mapped arena too. Every descriptor is checked before anything is copied or launched: an invalid
-// batch returns NEB_ERR_INVALID with the arena and the statuses untouched.
+// chunks of at most kPipeChunkPkts packets (pipe_plan) rotated over kPipeSlots device buffers: each
+// chunk's arena span is copied in (hipMemcpyAsync), sealed/opened on the device and copied back on
+// three streams, so one chunk's copy-in overlaps another's kernel and another's copy-back.
+// NEB_HOST_MODE=dma forces the staging for a mapped arena too. Every descriptor is checked before
+// anything is copied or launched: an invalid batch returns NEB_ERR_INVALID with the arena and the
+// statuses untouched.
 static int batch_host(neb_engine* e, int alg, int open, const neb_desc* desc, uint32_t n, uint8_t* arena,
                       size_t arena_len, int32_t* status, uint32_t key_hint) {
     int rc = check_batch(e, alg, key_hint);
@@ -1447,195 +1436,65 @@ static int batch_host(neb_engine* e, int alg, int open, const neb_desc* desc, ui
         return batch_host_zero_copy(e, alg, open, desc, n, arena, arena_len, status, key_hint);
     }
     Pipe& P = e->pipe;
-    // Each of the pipeline's streams on a hardware queue of its own: a stream with a CU mask gets
-    // one (all CUs here; tools/native/queue_map.cpp), where default streams share the process's 4
-    // and two of the pipeline's could land on one, so a chunk's kernel queued behind the previous
-    // chunk's copy back. NEB_PIPE_QUEUES=0: default streams, 2: low-priority streams (also a queue
-    // each) (A/B).
-    static const int own_queues = [] {
-        const char* v = std::getenv("NEB_PIPE_QUEUES");
-        return v ? std::atoi(v) : 1;
-    }();
-    for (hipStream_t* st : {&P.h2d, &P.comp, &P.d2h}) {
-        if (*st) continue;
-        if (own_queues == 2) {
-            int least = 0, greatest = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIP_TRY(hipStreamCreateWithPriority(st, hipStreamNonBlocking, least));
-        } else if (own_queues == 1) {
-            std::vector<uint32_t> mask(((uint32_t)e->cu_count + 31u) / 32u, 0u);
-            for (int c = 0; c < e->cu_count; c++) mask[c / 32] |= 1u << (c % 32);
-            HIP_TRY(hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()));
-        } else {
-            HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-        }
-    }
-    if (!P.sched && !(P.sched = new (std::nothrow) SchedSpace)) return NEB_ERR_INVALID;
-    for (auto& s : P.slot) {
-        if (!s.done) {
-            for (hipEvent_t* ev : {&s.in_done, &s.k_done, &s.done})
-                HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-            HIP_TRY(hipHostMalloc((void**)&s.h_desc, kPipeChunkPkts * sizeof(neb_desc), hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void**)&s.d_desc, kPipeChunkPkts * sizeof(neb_desc)));
-            HIP_TRY(hipHostMalloc((void**)&s.h_status, kPipeChunkPkts * sizeof(int32_t), hipHostMallocDefault));
-        }
-        s.count = 0;
-    }
-    auto retire = [](PipeSlot& s) -> hipError_t {
-        hipError_t err = hipEventSynchronize(s.done);
-        if (err != hipSuccess) return err;
-        std::memcpy(s.user_status + s.user_begin, s.h_status, s.count * sizeof(int32_t));
-        s.count = 0;
-        s.back_pending = false;
-        return hipSuccess;
-    };
-    // A slot taken for the next chunk: the host waits for the previous chunk's copy back (retire).
-    // In the trace each copy-in then starts as the copy back two chunks before it ends, 284 µs per
-    // call idle on the copy-in stream (profiles/r6/host/final_*_trace.csv, tools/r6/
-    // copy_overlap.py). Two ways of removing that wait measured no better: NEB_PIPE_GPU_WAIT=1
-    // waits only for the kernel on the host and for the copy back on the device (hipStreamWaitEvent
-    // before the copy-in), 27.9-29.3 against 31.7-33.4 GiB/s (ab_gpu_wait.jsonl); an empty kernel
-    // after each copy back with the event after it, 30.5-32.3 against 31.3-32.9 (ab_mark.jsonl).
-    static const bool gpu_wait = [] {
-        const char* v = std::getenv("NEB_PIPE_GPU_WAIT");
-        return v && v[0] == '1';
-    }();
-    auto reuse = [&](PipeSlot& s) -> hipError_t {
-        if (!gpu_wait) return retire(s);
-        hipError_t err = hipEventSynchronize(s.k_done);
-        if (err != hipSuccess) return err;
-        std::memcpy(s.user_status + s.user_begin, s.h_status, s.count * sizeof(int32_t));
-        s.count = 0;
-        s.back_pending = true;
-        return hipSuccess;
-    };
+    if ((rc = P.ensure(e)) != NEB_OK) return rc;
     // any failure below leaves work queued on the three streams: drain them before returning
-    auto fail = [&](const char* where, hipError_t err) {
-        set_error(where, err);
-        for (hipStream_t st : {P.h2d, P.comp, P.d2h}) (void)hipStreamSynchronize(st);
-        for (auto& s : P.slot) s.count = 0, s.back_pending = false;
-        return NEB_ERR_HIP;
-    };
-#define PIPE_TRY(x)                                     \
-    do {                                                \
-        hipError_t err_ = (x);                          \
-        if (err_ != hipSuccess) return fail(#x, err_);  \
+#define PIPE_TRY(x)                  \
+    do {                             \
+        hipError_t err_ = (x);       \
+        if (err_ != hipSuccess) {    \
+            set_error(#x, err_);     \
+            P.drain();               \
+            return NEB_ERR_HIP;      \
+        }                            \
     } while (0)
-    const std::vector<uint32_t> plan = pipe_plan(n);
-    bool arena_mapped = false;
+    const std::vector<uint32_t> plan = neb::pipe_plan(n);
     uint32_t begin = 0;
     for (uint32_t k = 0; k < plan.size(); begin += plan[k], k++) {
         PipeSlot& s = P.slot[k % kPipeSlots];
-        if (s.count) PIPE_TRY(reuse(s));  // the slot's previous chunk's kernel is done
         const uint32_t cnt = plan[k];
-        if (!check_upto(begin + cnt)) {  // (only ever the first chunk: the rest were checked after it)
-            for (hipStream_t st : {P.h2d, P.comp, P.d2h}) (void)hipStreamSynchronize(st);
-            for (auto& o : P.slot) o.count = 0, o.back_pending = false;
+        if (s.count) PIPE_TRY(P.retire(s));  // the slot's previous chunk is back
+        if (!check_upto(begin + cnt)) {      // (only ever the first chunk: the rest were checked after it)
+            P.drain();
             return NEB_ERR_INVALID;
         }
-        uint64_t lo = ~0ULL, hi = 0;  // every sum below stays within arena_len (checked above)
-        for (uint32_t i = 0; i < cnt; i++) {
-            const neb_desc& d = desc[begin + i];
-            const uint64_t pay = (uint64_t)d.len + (open ? 16u : 0u), outl = (uint64_t)d.len + (open ? 0u : 16u);
-            lo = std::min({lo, d.src_off, d.dst_off, d.aad_off});
-            hi = std::max({hi, d.src_off + pay, d.dst_off + outl, d.aad_off + d.aad_len});
-        }
-        lo &= ~(uint64_t)15;
         // A chunk copies its whole span back, so spans of chunks in flight must not overlap (the
         // descriptors need not be in arena order): retire any other slot whose span intersects.
-        // (A slot whose statuses are taken but whose copy back may still run: the copy-in waits for it.)
-        for (auto& o : P.slot) {
-            if (&o == &s || !(o.lo < hi && lo < o.hi)) continue;
-            if (o.count) PIPE_TRY(retire(o));
-            else if (o.back_pending) PIPE_TRY(hipStreamWaitEvent(P.h2d, o.done, 0));
-        }
-        s.lo = lo;
-        s.hi = hi;
-        const size_t span = (size_t)(hi - lo);
-        if (span > s.d_cap) {  // (retired: nothing in flight uses it)
-            if (s.back_pending) PIPE_TRY(hipEventSynchronize(s.done));
-            s.back_pending = false;
+        const neb::PipeSpan sp = neb::pipe_span(desc + begin, cnt, open);
+        for (auto& o : P.slot)
+            if (&o != &s && o.count && o.span.overlaps(sp)) PIPE_TRY(P.retire(o));
+        const size_t bytes = (size_t)(sp.hi - sp.lo);
+        if (bytes > s.d_cap) {  // (retired: nothing in flight uses it)
             if (s.d_buf) { hipFree(s.d_buf); s.d_buf = nullptr; s.d_cap = 0; }
-            size_t cap = align_up(span, 1 << 20);
+            const size_t cap = align_up(bytes, 1 << 20);
             PIPE_TRY(hipMalloc((void**)&s.d_buf, cap));
             s.d_cap = cap;
         }
-#ifndef NEB_PIPE_MODE  // A/B: 0 copies back on a stream of their own, 1 on the kernels' stream, 2 the kernels store into the arena
-#define NEB_PIPE_MODE 0
-#endif
-        // mode 2: the outputs go straight to the host arena (a wrapping offset from the device buffer)
-        const uint64_t out_rebase = NEB_PIPE_MODE == 2 ? (uint64_t)(uintptr_t)(arena + lo) - (uint64_t)(uintptr_t)s.d_buf : 0u;
-        for (uint32_t i = 0; i < cnt; i++) {
-            neb_desc d = desc[begin + i];
-            d.src_off -= lo;
-            d.aad_off -= lo;
-            d.dst_off = d.dst_off - lo + out_rebase;
-            s.h_desc[i] = d;
-        }
+        neb::pipe_rebase(s.h_desc, desc + begin, cnt, sp.lo);
+        s.span = sp;
         s.user_status = status;
         s.user_begin = begin;
         s.count = cnt;
+        PIPE_TRY(hipMemcpyAsync(s.d_buf, arena + sp.lo, bytes, hipMemcpyHostToDevice, P.h2d));
+        PIPE_TRY(hipEventRecord(s.in_done, P.h2d));
         // The kernels write the chunk's statuses in the slot's pinned, mapped buffer themselves (4 B
         // per packet of posted writes). Its descriptors go to the device on the kernels' stream,
         // ahead of them: read over PCIe in place they waited behind the copies' 90 GB/s, and the
         // kernels ran 250-478 µs per 16 Ki-packet chunk instead of ≈ 25 (profiles/r6/host/); on the
         // copy-in stream the small copy's latency left that stream idle between chunks.
-        static const int desc_dev = [] {  // NEB_PIPE_DESC=0: read in place, 2: hipMemcpyAsync (A/B)
-            const char* v = std::getenv("NEB_PIPE_DESC");
-            return v ? std::atoi(v) : 1;
-        }();
-        // NEB_PIPE_COPY (A/B): bit 0 copies back with a kernel of ours instead of hipMemcpyAsync, bit
-        // 1 copies in with one. Only for an arena the device can address (pinned and mapped at both
-        // ends: a kernel touching pageable memory faults the GPU) at the same address mod 16 as its
-        // device buffer; anything else takes hipMemcpyAsync.
-        static const int copy_k = [] {
-            const char* v = std::getenv("NEB_PIPE_COPY");
-            return v ? std::atoi(v) : 0;
-        }();
-        if (k == 0) arena_mapped = copy_k && arena_len && host_mapped(arena) && host_mapped(arena + arena_len - 1);
-        auto copy = [&](void* dst, const void* src, hipMemcpyKind kind, hipStream_t st) {
-            if (arena_mapped && (copy_k & (kind == hipMemcpyDeviceToHost ? 1 : 2)) &&
-                neb_copy_span(dst, src, span, st) == hipSuccess)
-                return hipSuccess;
-            (void)hipGetLastError();
-            return hipMemcpyAsync(dst, src, span, kind, st);
-        };
-        if (s.back_pending) PIPE_TRY(hipStreamWaitEvent(P.h2d, s.done, 0));
-        s.back_pending = false;
-        PIPE_TRY(copy(s.d_buf, arena + lo, hipMemcpyHostToDevice, P.h2d));
-        PIPE_TRY(hipEventRecord(s.in_done, P.h2d));
-        if (NEB_PIPE_MODE == 2 && k == 0 && !check_upto(n)) {  // (mode 2's kernels write the arena)
-            for (hipStream_t st : {P.h2d, P.comp, P.d2h}) (void)hipStreamSynchronize(st);
-            for (auto& o : P.slot) o.count = 0, o.back_pending = false;
-            return NEB_ERR_INVALID;
-        }
         PIPE_TRY(hipStreamWaitEvent(P.comp, s.in_done, 0));
-        if (desc_dev == 2)
-            PIPE_TRY(hipMemcpyAsync(s.d_desc, s.h_desc, cnt * sizeof(neb_desc), hipMemcpyHostToDevice, P.comp));
-        else if (desc_dev)
-            PIPE_TRY(neb_copy_desc(s.d_desc, s.h_desc, cnt, P.comp));
-        PIPE_TRY(launch_batch(e, alg, open, desc_dev ? s.d_desc : s.h_desc, cnt, s.d_buf, s.h_status, key_hint, P.comp,
-                              nullptr, P.sched));
+        PIPE_TRY(neb_copy_desc(s.d_desc, s.h_desc, cnt, P.comp));
+        PIPE_TRY(launch_batch(e, alg, open, s.d_desc, cnt, s.d_buf, s.h_status, key_hint, P.comp, nullptr, P.sched));
         PIPE_TRY(hipEventRecord(s.k_done, P.comp));
         if (k == 0 && !check_upto(n)) {  // the rest of the batch, while chunk 0 is copied in and run
-            for (hipStream_t st : {P.h2d, P.comp, P.d2h}) (void)hipStreamSynchronize(st);
-            for (auto& o : P.slot) o.count = 0, o.back_pending = false;
+            P.drain();
             return NEB_ERR_INVALID;
         }
-        if (NEB_PIPE_MODE == 2) {
-            PIPE_TRY(hipEventRecord(s.done, P.comp));
-        } else {
-            hipStream_t back = NEB_PIPE_MODE == 1 ? P.comp : P.d2h;
-            if (NEB_PIPE_MODE == 0) PIPE_TRY(hipStreamWaitEvent(P.d2h, s.k_done, 0));
-            PIPE_TRY(copy(arena + lo, s.d_buf, hipMemcpyDeviceToHost, back));
-            PIPE_TRY(hipEventRecord(s.done, back));
-        }
+        PIPE_TRY(hipStreamWaitEvent(P.d2h, s.k_done, 0));
+        PIPE_TRY(hipMemcpyAsync(arena + sp.lo, s.d_buf, bytes, hipMemcpyDeviceToHost, P.d2h));
+        PIPE_TRY(hipEventRecord(s.done, P.d2h));
     }
-    for (auto& s : P.slot) {
-        if (s.count) PIPE_TRY(retire(s));
-        if (s.back_pending) PIPE_TRY(hipEventSynchronize(s.done));  // every copy back is in the arena
-        s.back_pending = false;
-    }
+    for (auto& s : P.slot)
+        if (s.count) PIPE_TRY(P.retire(s));
 #undef PIPE_TRY
     return NEB_OK;
 }
@@ -1768,12 +1627,12 @@ static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, c
                         d_pk_status, d_nwires, s));
     // one tunnel key with AES-GCM: the seal sums the payload into the L4 checksums itself, so the
     // segment kernel does not read the payload (aes_gcm.hip gcm_csum_fix)
-    const bool cs = neb::kTxSealFromInput && NEB_TX_CSUM_SEAL && alg == NEB_ALG_AESGCM && key_hint != NEB_KEYS_MIXED;
+    const bool cs = alg == NEB_ALG_AESGCM && key_hint != NEB_KEYS_MIXED;
     const uint32_t cs_slots = cs ? neb_gcm_single_slots(max_wires, e->cu_count, 0, 2) : 0u;
     HIP_TRY(neb_tx_segment(d_pk, npk, d_in, d_tun, d_via, d_out, &tx.ws, d_wires, d_nwires, max_wires, e->cu_count,
                            cs_slots, s));
     HIP_TRY(launch_batch(e, alg, 0, tx.ws.seal_desc, max_wires, d_out, d_wire_status, key_hint, s, d_nwires, nullptr,
-                         cs ? 2 : (int)neb::kTxSealFromInput));
+                         cs ? 2 : 1));  // hdr_from_dst: the seal reads the payload from the TUN read
     HIP_TRY(neb_tx_finish(d_tun, npk, ntun, &tx.ws, s));
     if (d_via && max_wires) {
         // prepareSendVia's tags: the AD-only seal over the compacted via wires, behind the inner seal

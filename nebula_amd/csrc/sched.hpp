@@ -79,16 +79,13 @@ constexpr uint32_t kSmallBatchPerWave = NEB_SMALL_BATCH_PER_WAVE, kSmallBatchGro
 // counters[] slots
 constexpr uint32_t kCntPackets = 0;  // cursor into sorted[]
 constexpr uint32_t kCntBucket = 1;   // [kBuckets] chunks filed in each cost bucket
-#ifndef NEB_CHUNK_STEAL  // gcm_chunk_kernel: the last 1/NEB_CHUNK_STEAL of a batch's chunks drawn per XCD (0: off)
+#ifndef NEB_CHUNK_STEAL  // gcm_chunk_kernel: the last 1/NEB_CHUNK_STEAL of a batch's chunks drawn per XCD
 #define NEB_CHUNK_STEAL 8
 #endif
-#if NEB_CHUNK_STEAL
+static_assert(NEB_CHUNK_STEAL >= 1, "a fraction of the chunks: every chunk owned was removed");
 // the chunk kernel's per-XCD cursors over the batch's last chunks, 128 B apart (gcm_chunk_kernel)
 constexpr uint32_t kCntSteal = 32, kStealStride = 32;
 constexpr uint32_t kSchedCounters = kCntSteal + 8 * kStealStride;
-#else
-constexpr uint32_t kSchedCounters = 16;
-#endif
 // sorted[] entry of a packet the crypto kernel must skip (the device receive's refused packets)
 constexpr uint32_t kSortedSkip = 0xFFFFFFFFu;
 

@@ -722,16 +722,12 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
             // an exhausted outer counter drops the wire: the inner seal reports it from this counter
             const uint64_t seal_ctr = outer_dead ? rctr : counter;
             const uint64_t islot = slot + vo;
-            if constexpr (kTxSealFromInput) {
-                // plaintext byte x of the segment image: x < hdr from the slot (the patched header, or
-                // a plain packet up to its finished checksum), else the TUN read's byte in_off + a + x
-                const uint32_t kind = (plan.kind == kTxUdp || (plan.kind == kTxFinish && co == 6u)) ? 2u : 1u;
-                const uint32_t fl = seal_cs ? hdr_b | fld << 12 | kind << 24 | (cs & 1u) << 26 : hdr_b;
-                const uint64_t src = (uint64_t)((uintptr_t)(in + P.in_off + a) - (uintptr_t)out);
-                ws.seal_desc[s] = neb_desc{src, islot + 16u, islot, seal_ctr, seg_len, 16u, T.key_id, fl};
-            } else {
-                ws.seal_desc[s] = neb_desc{islot + 16u, islot + 16u, islot, seal_ctr, seg_len, 16u, T.key_id, 0u};
-            }
+            // plaintext byte x of the segment image: x < hdr from the slot (the patched header, or
+            // a plain packet up to its finished checksum), else the TUN read's byte in_off + a + x
+            const uint32_t kind = (plan.kind == kTxUdp || (plan.kind == kTxFinish && co == 6u)) ? 2u : 1u;
+            const uint32_t fl = seal_cs ? hdr_b | fld << 12 | kind << 24 | (cs & 1u) << 26 : hdr_b;
+            const uint64_t src = (uint64_t)((uintptr_t)(in + P.in_off + a) - (uintptr_t)out);
+            ws.seal_desc[s] = neb_desc{src, islot + 16u, islot, seal_ctr, seg_len, 16u, T.key_id, fl};
             if (VIA && vo && work) {
                 // prepareSendVia (inside.go:442-501): header.Encode(1, Message, MessageRelay,
                 // relay.RemoteIndex, r), and the tag over everything before it
@@ -815,10 +811,9 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
         const uint32_t zlo = plan.kind == kTxFinish ? cs + co : 0u, zhi = plan.kind == kTxFinish ? cs + co + 2u : 0u;
         const uint8_t* psrc = src + hl + a;
         const uint32_t nunits = !work ? 0u : seal_cs ? min((pl + 15u) >> 4, (hdr_b + 15u) >> 4) : (pl + 15u) >> 4;
-        const bool in_regs = !kTxSealFromInput && nunits <= kTxGroup * kTxRegUnits;
         const bool flip = ((hl ^ sum_lo) & 1u) != 0u;  // units start at the parity of hl
         uint4 keep[kTxRegUnits];
-        if (kTxSealFromInput && !CSM) {
+        if (!CSM) {
             // the checksum only: kTxRegUnits loads in flight per lane, then their sums
             if (need_sum) {
                 for (uint32_t u0 = 0; u0 < nunits; u0 += kTxGroup * kTxRegUnits) {
@@ -841,28 +836,6 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
                             const uint32_t su = unit_le_sum(v);
                             le += flip ? bswap16(fold16(su)) : su;
                         }
-                    }
-                }
-            }
-        } else if (in_regs) {
-#pragma unroll
-            for (uint32_t k = 0; k < kTxRegUnits; k++) {
-                const uint32_t u = g + kTxGroup * k;
-                keep[k] = make_uint4(0, 0, 0, 0);
-                if (u < nunits) keep[k] = load_block(psrc + 16u * u, min(16u, pl - 16u * u));
-            }
-            if (need_sum) {
-#pragma unroll
-                for (uint32_t k = 0; k < kTxRegUnits; k++) {
-                    const uint32_t u = g + kTxGroup * k;
-                    if (u < nunits) {
-                        uint4 v = keep[k];
-                        if (plan.kind == kTxFinish) {  // only FinishChecksum sums part of its units
-                            v = zero_range(v, hl + 16u * u, 0u, sum_lo);
-                            v = zero_range(v, hl + 16u * u, zlo, zhi);
-                        }
-                        const uint32_t su = unit_le_sum(v);
-                        le += flip ? bswap16(fold16(su)) : su;
                     }
                 }
             }
@@ -910,32 +883,13 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
                 }
             }
         }
-        if (kTxSealFromInput) {
-            // a plain packet's prefix up to its finished checksum; the seal reads the rest from the read
-            if (work && plan.kind == kTxFinish) {
-                const uint32_t hdr = cs + co + 2u;
-                for (uint32_t u = g; 16u * u < hdr; u += kTxGroup) {
-                    const uint32_t nb = min(16u, hdr - 16u * u);
-                    const uint4 v = put_be_unit(load_block(psrc + 16u * u, nb), 16u * u, cs + co, csum);
-                    store_block(ddst + 16u * u, v, nb);
-                }
-            }
-        } else if (in_regs) {
-#pragma unroll
-            for (uint32_t k = 0; k < kTxRegUnits; k++) {
-                const uint32_t u = g + kTxGroup * k;
-                if (u < nunits) {
-                    uint4 v = keep[k];
-                    if (plan.kind == kTxFinish) v = put_be_unit(v, hl + 16u * u, cs + co, csum);
-                    store_block(ddst + hl + 16u * u, v, min(16u, pl - 16u * u));
-                }
-            }
-        } else {
-            for (uint32_t u = g; u < nunits; u += kTxGroup) {
-                const uint32_t nb = min(16u, pl - 16u * u);
-                uint4 v = load_block(psrc + 16u * u, nb);
-                if (plan.kind == kTxFinish) v = put_be_unit(v, hl + 16u * u, cs + co, csum);
-                store_block(ddst + hl + 16u * u, v, nb);
+        // a plain packet's prefix up to its finished checksum; the seal reads the rest from the read
+        if (work && plan.kind == kTxFinish) {
+            const uint32_t hdr = cs + co + 2u;
+            for (uint32_t u = g; 16u * u < hdr; u += kTxGroup) {
+                const uint32_t nb = min(16u, hdr - 16u * u);
+                const uint4 v = put_be_unit(load_block(psrc + 16u * u, nb), 16u * u, cs + co, csum);
+                store_block(ddst + 16u * u, v, nb);
             }
         }
     }
@@ -1000,10 +954,6 @@ extern "C" size_t neb_tx_ws_bytes(uint32_t n, uint32_t ntun, uint32_t max_wires,
     return neb::tx_ws_layout(n, ntun, max_wires, *cub_bytes, nullptr, nullptr);
 }
 
-#ifndef NEB_TX_SMALL_PLAN
-#define NEB_TX_SMALL_PLAN 1
-#endif
-
 extern "C" hipError_t neb_tx_plan(const neb_tx_packet* d_pk, uint32_t n, const uint8_t* d_in,
                                   neb_tx_tunnel* d_tun, uint32_t ntun, const neb_relay_route* d_via,
                                   const uint32_t* d_keys, uint32_t max_keys, int alg, const neb::TxWs* ws,
@@ -1011,7 +961,7 @@ extern "C" hipError_t neb_tx_plan(const neb_tx_packet* d_pk, uint32_t n, const u
                                   hipStream_t s) {
     int bits = 1;
     while (bits < 32 && (1ull << bits) <= ntun) bits++;
-    if (NEB_TX_SMALL_PLAN && n <= neb::kTxPlanSmallMax) {
+    if (n <= neb::kTxPlanSmallMax) {
         // Parsing is a chain of dependent header loads per read: past one read per lane of the one
         // workgroup it runs grid-wide first (1457 reads: plan 24.8 -> the two kernels below).
         const bool pre = n > neb::kTxPlanThreads;
@@ -1114,7 +1064,7 @@ extern "C" hipError_t neb_tx_via_fix(const neb::TxWs* ws, uint32_t max_wires, in
 
 extern "C" hipError_t neb_tx_finish(neb_tx_tunnel* d_tun, uint32_t n, uint32_t ntun, const neb::TxWs* ws,
                                     hipStream_t s) {
-    if (ntun == 0 || (NEB_TX_SMALL_PLAN && n <= neb::kTxPlanSmallMax)) return hipSuccess;  // done by the plan kernel
+    if (ntun == 0 || n <= neb::kTxPlanSmallMax) return hipSuccess;  // done by the plan kernel
     hipLaunchKernelGGL(neb::tx_finish_kernel, dim3((ntun + 255) / 256), dim3(256), 0, s, d_tun, ntun, *ws);
     return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 """Host model of gcm_chunk_kernel's chunk claims (nebula_amd/csrc/aes_gcm.hip):
 workgroup b owns chunks b, b + G, b + 2G, ... below nstat, its waves draw them from an LDS cursor
-(the first 16 without it), and with NEB_CHUNK_STEAL the last nch / 8 chunks are drawn from one
+(the first 16 without it), and the last nch / 8 chunks (1 / NEB_CHUNK_STEAL) are drawn from one
 cursor per XCD (blockIdx mod 8), partition x holding chunks nstat + x + 8d. Every chunk must be run
 exactly once, whatever order the waves draw in."""
 import random

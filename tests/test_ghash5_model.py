@@ -1,4 +1,4 @@
-"""CPU model of the single-key kernel's 5-bit window GHASH multiply (gf_mul_full5, NEB_GHASH5):
+"""CPU model of the single-key kernel's 5-bit window GHASH multiply (gf_mul_full5):
 the table F5[P][v] = (v·x^5P)·H^4 derived from the key record's nibble table exactly as the kernel
 prologue derives it, laid out in LDS as two 256-byte rows of 8-byte halves per window, and the
 window extraction of the multiply (shifts, and an alignbit for the windows that straddle two

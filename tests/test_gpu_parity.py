@@ -512,6 +512,58 @@ def test_host_modes_shuffled_descriptors(engine, oracle_mod, mode, knobs):
             c.destroy()
 
 
+_SLOT_REUSE = {}
+
+
+def _slot_reuse_case(oracle_mod):
+    """The batch both slot-reuse cases run, with the oracle's sealed and opened arenas (made once)."""
+    if not _SLOT_REUSE:
+        b = W.make_batch(L.ALG_AESGCM, 40960, 64, sizes=(90,), name="slot-reuse")
+        ref, _ = oracle_seal(oracle_mod, b)
+        ref_o, _ = oracle_open(oracle_mod, b, ref)
+        for a in (b.arena, ref, ref_o):
+            a.setflags(write=False)
+        _SLOT_REUSE.update(b=b, ref=ref, ref_o=ref_o)
+    return _SLOT_REUSE["b"], _SLOT_REUSE["ref"], _SLOT_REUSE["ref_o"]
+
+
+@pytest.mark.parametrize("order", ["in_order", "shuffled"])
+def test_host_staged_pipeline_reuses_slot(engine, oracle_mod, order, knobs):
+    """The staged pipeline (KNOB_HOST_MODE = 1) past its four slots: 40960 packets of 90 B, mixed
+    keys, are planned as [4096, 8192, 16384, 8192, 4096], the smallest batch whose fifth chunk must
+    retire slot 0 before it reuses it. in_order: a pageable arena with the descriptors in arena
+    order, so the chunks' spans are disjoint and only the reuse retires anything. shuffled: a pinned
+    arena with the descriptors permuted, so every chunk's span covers nearly the whole arena and each
+    new chunk retires the other slots by overlap as well. Seal, then open; the arena equals the
+    oracle's byte for byte and every status is 0."""
+    from nebula_amd.batch import PinnedBuffer, host_batch, install_keys, slot_desc
+
+    knobs(L.KNOB_HOST_MODE, 1)
+    b, ref, ref_o = _slot_reuse_case(oracle_mod)
+    ciphers = install_keys(engine, b)
+    buf = None
+    try:
+        d = slot_desc(b, ciphers)
+        if order == "shuffled":
+            d = d[np.random.default_rng(11).permutation(b.n)]
+            buf = PinnedBuffer(b.arena.nbytes)
+            arena = buf.array
+            arena[:] = b.arena
+        else:
+            arena = b.arena.copy()
+        st = host_batch(engine, b.alg, False, d, arena)
+        assert (st == 0).all()
+        assert np.array_equal(arena, ref)
+        st = host_batch(engine, b.alg, True, d, arena)
+        assert (st == 0).all()
+        assert np.array_equal(arena, ref_o)
+    finally:
+        if buf is not None:
+            buf.free()
+        for c in ciphers:
+            c.destroy()
+
+
 def test_host_zero_copy_rejects_out_of_bounds(engine):
     """A descriptor past the pinned arena is refused before any kernel touches host memory."""
     from nebula_amd.batch import PinnedBuffer, host_batch, install_keys, slot_desc
