@@ -13,6 +13,8 @@ Sources, in order of authority:
      (tags committed) in batches.json, and the full C2-C5 batches (64 Ki x 1300 B; 1 Mi IMIX)
      as SHA-256 digests of the whole sealed and opened arenas in full_digests.json
      (`--no-full` skips them: about a minute on 8 cores).
+  4. Directed Poly1305 packets solved by tests/poly1305_ref.py (poly1305_edges.json), sealed by the
+     oracle and EVP under the same rule (`--only-poly1305` writes kat.json and this file only).
 
 The Go reference itself cannot run here (no Go toolchain), so (3) is pinned by (1)+(2) through
 the oracle, not by Go output.
@@ -138,10 +140,41 @@ def sealed_digest(b):
     return arena, tags
 
 
+def poly1305_edges_json():
+    """tests/golden/poly1305_edges.json as text: the directed Poly1305 packets of
+    tests/poly1305_ref.py (accumulator values at the edges of the final reduction, in a relay and
+    a data shape, and the all-0xFF packets), each with the sealed bytes the plain-C oracle and
+    OpenSSL EVP agree on. The Python helper that solved them is a third opinion, checked in
+    tests/test_poly1305_vectors.py."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import poly1305_ref
+
+    vecs = poly1305_ref.vectors()
+    for v in vecs:
+        key, aad, pt = (np.frombuffer(bytes.fromhex(v[k]), np.uint8) for k in ("key", "aad", "plaintext"))
+        src = (len(aad) + 15) // 16 * 16
+        arena = np.zeros(src + len(pt) + 16, np.uint8)
+        arena[:len(aad)] = aad
+        arena[src:src + len(pt)] = pt
+        d = np.zeros(1, oracle.DESC_DTYPE)
+        d[0] = (src, src, 0, v["counter"], len(pt), len(aad), 0, 0)
+        a1, a2 = arena.copy(), arena.copy()
+        st = oracle.batch(oracle.CHACHA, 0, key.copy(), d, a1)
+        _, st2 = oracle.evp_batch(oracle.CHACHA, 0, key.copy(), d, a2)
+        if st[0] or st2[0] or not np.array_equal(a1, a2):
+            raise SystemExit(f"oracle and OpenSSL EVP disagree on {v['shape']}/{v['target']} — refusing to write")
+        v["sealed"] = a1[src:].tobytes().hex()
+    return json.dumps(vecs, indent=1) + "\n"
+
+
 def main():
     oracle.build()
     with open(os.path.join(OUT, "kat.json"), "w") as f:
         json.dump(KAT, f, indent=1)
+    with open(os.path.join(OUT, "poly1305_edges.json"), "w") as f:
+        f.write(poly1305_edges_json())
+    if "--only-poly1305" in sys.argv:
+        return
     meta = {}
     for name, mk in BATCHES.items():
         b = mk()

@@ -254,6 +254,28 @@ def test_unaligned_offsets(engine, oracle_mod, alg):
     got, st = run_device(engine, b, seal=True)
     assert (st == 0).all()
     assert np.array_equal(got, ref)
+    _open_back(engine, oracle_mod, b, ref)
+
+
+def _open_back(engine, oracle_mod, b, sealed):
+    """Open the oracle-sealed arena of a batch whose seal was partly out of place: from where the
+    seal wrote to where it read, those plaintext bytes overwritten first so that the open has to
+    write every one of them. Bit-exact against the oracle, every status 0."""
+    d = b.desc.copy()
+    d["src_off"], d["dst_off"] = b.desc["dst_off"], b.desc["src_off"]
+    t = sealed.copy()
+    for i in np.flatnonzero(d["src_off"] != d["dst_off"]):
+        s, ln = int(d["dst_off"][i]), int(d["len"][i])
+        t[s:s + ln] ^= 0xA5
+    ob = W.Batch(b.alg, b.keys, b.remote_index, d, b.arena, b.stride, b.name + "-open")
+    ref_o, st_ref = oracle_open(oracle_mod, ob, t)
+    assert (st_ref == 0).all()
+    for i in range(b.n):  # the oracle restored the plaintext
+        s, ln = int(d["dst_off"][i]), int(d["len"][i])
+        assert np.array_equal(ref_o[s:s + ln], b.arena[int(b.desc["src_off"][i]):int(b.desc["src_off"][i]) + ln])
+    got_o, st_o = run_device(engine, ob, seal=False, arena=t)
+    assert (st_o == 0).all()
+    assert np.array_equal(got_o, ref_o)
 
 
 @pytest.mark.parametrize("alg,nkeys", [(L.ALG_AESGCM, 1), (L.ALG_AESGCM, 8), (L.ALG_CHACHAPOLY, 8)])
@@ -280,6 +302,7 @@ def test_aligned_dst_skewed_src(engine, oracle_mod, alg, nkeys):
     got, st = run_device(engine, b, seal=True)
     assert (st == 0).all()
     assert np.array_equal(got, ref)
+    _open_back(engine, oracle_mod, b, ref)  # aligned sources, destinations at every byte skew
 
 
 @pytest.mark.parametrize("shift", [1, 4, 8])
