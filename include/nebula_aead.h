@@ -440,8 +440,8 @@ NEB_API int neb_tx_seal_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tunnel
  * Message/Relay header over the old one and a new tag under the outbound key where the old tag
  * was — one packet at a time ("it would potentially be nice to batch these", outside.go:239).
  * These calls do it for a whole receive batch. TerminalType relays (the inner packet is for this
- * node) are not unwrapped here: the caller gives them no route and receives the inner packets in
- * a batch of their own. */
+ * node) are not unwrapped here: the caller gives them no route and receives them with
+ * neb_rx_open_via_batch (below), which verifies, unwraps and opens them in one call. */
 #define NEB_RELAY_NONE 0xFFFFFFFFu
 #define NEB_STATUS_NOT_FORWARDED 8 /* fwd_status: not a verified Message/Relay packet, or no route */
 /* Per received packet: what the caller's relay lookups found for the header's remote index
@@ -483,6 +483,66 @@ NEB_API int neb_relay_forward_batch_host(neb_engine* e, int alg, neb_window* con
                                          const neb_rx_packet* pk, const neb_relay_route* route, uint32_t n,
                                          neb_tx_tunnel* tunnels, uint32_t ntunnels, uint8_t* arena, size_t arena_len,
                                          int32_t* status, int32_t* fwd_status, uint32_t key_hint);
+/* ---- receive through a relay: VerifyRelay, then unwrap and open, in one call --------------------- */
+/* A node reached through a relay gets every data packet wrapped: handleOutsideRelayPacket's
+ * TerminalType branch (outside.go:191-219) runs VerifyRelay on the outer packet through the relay
+ * tunnel's window, strips the outer header and tag (signedPayload = packet[16 : len-16]) and calls
+ * readOutsidePackets again on the inner packet with IsRelayed = true. These calls do both levels
+ * for a whole receive batch. */
+#define NEB_VIA_TERMINAL 1       /* relay.Type == TerminalType for the outer header's remote index
+                                    (relayState.QueryRelayForByIdx, outside.go:201-210) */
+#define NEB_STATUS_NOT_RELAYED 9 /* inner_status: no inner packet (not a verified terminal relay packet) */
+typedef struct neb_rx_via {      /* per received datagram, the caller's lookups for the INNER packet */
+    uint32_t key_id; /* tunnel resolved from the inner header's remote index (the header at off+16;
+                        the caller may look it up before anything is verified: it is used only if the
+                        outer packet verifies); NEB_KEYS_MIXED: none */
+    uint32_t flags;  /* NEB_VIA_TERMINAL */
+} neb_rx_via;
+/* Phase 1 (outer): status[], the arena and the windows are exactly what
+ * neb_rx_open_wire_batch[_host] gives for the same pk; key_hint applies to it.
+ * Unwrap, per packet i. Eligible: status[i] == NEB_STATUS_OK, the header is Message/Relay (type 1,
+ * subtype 1) and via[i].flags & NEB_VIA_TERMINAL. An eligible packet gets inner_pk[i] = {pk[i].off +
+ * 16, len - 32, via[i].key_id} (len without NEB_RX_OWN_SOURCE, which an inner record never carries:
+ * IsRelayed skips that check, outside.go:66). Every other packet gets inner_pk[i] = {pk[i].off, 0,
+ * NEB_KEYS_MIXED} and inner_status[i] = NEB_STATUS_NOT_RELAYED, no further write and no window event.
+ * Phase 2 (inner): the wire receive of neb_rx_open_wire_batch over inner_pk[] in arrival order
+ * writes inner_status[]: the same gate, windows and in-place open, with inner_key_hint. So an inner
+ * Decrypt opens in place at pk[i].off + 32 (the outer header, the inner header and the outer tag are
+ * not written); an inner packet shorter than 16 or than 32 bytes, hole punches among them, gets
+ * NEB_STATUS_INVALID, one with no tunnel NEB_STATUS_BAD_KEY, an inner handshake or recv error
+ * NEB_STATUS_NOT_MESSAGE. One exception to the gate: an inner packet that is itself Message/Relay
+ * (checked where the gate hands over the unencrypted types) is not verified and takes no window
+ * event: NEB_STATUS_NOT_MESSAGE, untouched, for the caller to feed into another call. That is one
+ * level of the reference's recursion per call; no sender produces nesting, a relay is always
+ * reached directly (inside.go:183-198).
+ * Order. The batch is the reference's loop with the recursion deferred: every datagram's own gate,
+ * Check, verify and Update run first, in arrival order; the recursive call of every terminal relay
+ * packet that verified runs afterwards, in arrival order. That equals the strict per-packet
+ * recursion whenever no tunnel takes a window event in both phases of one batch. Where one does (a
+ * peer heard directly and through a relay in the same batch), the outcome is the strict loop's for
+ * an arrival order with the direct packets first.
+ * inner_pk and inner_status are index-aligned with pk and go unchanged into neb_rx_plain_from_wire
+ * and neb_rx_coalesce_batch. n == 0 returns NEB_OK.
+ * Device form: device pointers; d->mu is held across both phases and the call returns with `stream`
+ * synchronized, as neb_rx_open_wire_batch does. A batch without an eligible packet costs one kernel
+ * in place of neb_rx_open_wire_batch's last and nothing more. */
+NEB_API int neb_rx_open_via_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk,
+                                  const neb_rx_via* d_via, uint32_t n, uint8_t* d_arena, int32_t* d_status,
+                                  neb_rx_packet* d_inner_pk, int32_t* d_inner_status, uint32_t key_hint,
+                                  uint32_t inner_key_hint, void* stream);
+/* The same over host memory (synchronous); every pk is checked against arena_len first
+ * (NEB_ERR_INVALID: nothing written). */
+NEB_API int neb_rx_open_via_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                                       const neb_rx_packet* pk, const neb_rx_via* via, uint32_t n, uint8_t* arena,
+                                       size_t arena_len, int32_t* status, neb_rx_packet* inner_pk,
+                                       int32_t* inner_status, uint32_t key_hint, uint32_t inner_key_hint);
+/* The unwrap rule alone, on the CPU (no engine): inner_pk[] and, for the packets that are not
+ * eligible, inner_status[] = NEB_STATUS_NOT_RELAYED; an eligible packet's inner_status is set to
+ * NEB_STATUS_OK, to be overwritten by the receive of inner_pk. Every pk is checked against arena_len
+ * first (NEB_ERR_INVALID: nothing written). */
+NEB_API int neb_rx_via_unwrap_host(const neb_rx_packet* pk, const neb_rx_via* via, const int32_t* status, uint32_t n,
+                                   const uint8_t* arena, size_t arena_len, neb_rx_packet* inner_pk,
+                                   int32_t* inner_status);
 /* ---- transmit through a relay: seal, then SendVia, in one call ---------------------------------- */
 /* sendInsideMessage with its relay branch (inside.go:178-223: `!remote.IsValid()`, the target is
  * reached only through a relay): neb_tx_seal_batch[_host] plus via[0..ntunnels). via[t].tunnel is

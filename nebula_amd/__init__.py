@@ -11,13 +11,15 @@ from .noiseutil import (CipherAESGCM, CipherChaChaPoly, CipherState, CipherState
                         Engine, ErrMessageCounterExhausted, ErrNoCipher, ErrOpen, NewCipherState,
                         RejectAfterMessages, RejectHeadroom, Slice)
 from .outside import MultiCoalescer, coalesce_batch_device, coalesce_batch_host, receive
-from .relay import relay_forward_batch, relay_forward_batch_device
+from .relay import (relay_forward_batch, relay_forward_batch_device, rx_open_via_batch, rx_open_via_batch_device,
+                    rx_via_unwrap)
 
 __all__ = [
     "ALG_AESGCM", "ALG_CHACHAPOLY", "DESC_DTYPE", "KEYS_MIXED", "OVERHEAD", "REJECT_AFTER_MESSAGES",
     "NebError", "build", "CipherAESGCM", "CipherChaChaPoly", "CipherState", "CipherStateAESGCM",
     "CipherStateChaChaPoly", "Engine", "ErrMessageCounterExhausted", "ErrNoCipher", "ErrOpen",
     "NewCipherState", "RejectAfterMessages", "RejectHeadroom", "Slice", "_lib",
-    "relay_forward_batch", "relay_forward_batch_device",
+    "relay_forward_batch", "relay_forward_batch_device", "rx_open_via_batch", "rx_open_via_batch_device",
+    "rx_via_unwrap",
     "MultiCoalescer", "coalesce_batch_host", "coalesce_batch_device", "receive",
 ]

@@ -37,6 +37,7 @@ STATUS_INVALID = 5
 STATUS_NO_SPACE = 6
 STATUS_NOT_MESSAGE = 7
 STATUS_NOT_FORWARDED = 8  # relay forwarding: not a verified Message/Relay packet, or no route
+STATUS_NOT_RELAYED = 9  # neb_rx_open_via_batch's inner_status: not a verified terminal relay packet
 
 OVERHEAD = 16
 HEADER_LEN = 16
@@ -49,6 +50,7 @@ KNOB_SMALL_BATCH, KNOB_FRONT_GROUPS = 5, 6
 KNOB_COALESCE_HASH_BITS = 7  # the device coalescer's flow hash keeps this many bits (tests: collisions)
 RELAY_NONE = 0xFFFFFFFF  # neb_relay_route.tunnel: do not forward (neb_tx_seal_via_batch: sent directly)
 TX_WIRE_VIA = 1  # neb_tx_wire.reserved of a wire sent through a relay (neb_tx_seal_via_batch)
+VIA_TERMINAL = 1  # neb_rx_via.flags: the outer header's relay is a TerminalType (the inner packet is ours)
 RX_OWN_SOURCE = 0x80000000  # or-ed into neb_rx_packet.len: outside.go:66-74 refused the datagram
 
 # neb_desc (include/nebula_aead.h)
@@ -63,6 +65,9 @@ assert RX_PACKET_DTYPE.itemsize == 16
 # neb_relay_route (include/nebula_aead.h): where a relayed packet goes (RELAY_NONE: nowhere)
 RELAY_ROUTE_DTYPE = np.dtype([("tunnel", "<u4"), ("remote_index", "<u4")])
 assert RELAY_ROUTE_DTYPE.itemsize == 8
+# neb_rx_via (include/nebula_aead.h): the caller's lookups for the packet inside a relay packet
+RX_VIA_DTYPE = np.dtype([("key_id", "<u4"), ("flags", "<u4")])
+assert RX_VIA_DTYPE.itemsize == 8
 
 # neb_plain_packet (include/nebula_aead.h): one MultiCoalescer.Commit
 PLAIN_PARSED, PLAIN_FRAG_ANY, PLAIN_SKIP = 1, 2, 4
@@ -137,6 +142,9 @@ SIGNATURES = {
     "neb_rx_open_wire_batch": (_i, [_vp, _i, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "neb_relay_forward_batch": (_i, [_vp, _i, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "neb_relay_forward_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _vp, _u32]),
+    "neb_rx_open_via_batch": (_i, [_vp, _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "neb_rx_open_via_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _vp, _vp, _vp, _u32, _u32]),
+    "neb_rx_via_unwrap_host": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
     "neb_rx_coalesce_batch": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "neb_rx_coalesce_batch_host": (_i, [_vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32]),
     "neb_rx_plain_from_wire": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),

@@ -568,6 +568,104 @@ __global__ __launch_bounds__(256) void rx_wire_fix_kernel(const int32_t* __restr
     if (i < n && gate[i] != NEB_STATUS_OK) status[i] = gate[i];
 }
 
+// neb_rx_open_via_batch, in place of rx_wire_fix_kernel: the same fix, then the terminal-relay unwrap
+// (neb_rx_via_unwrap) of the finished outer packet. One lane per packet: status, gate, pk and via
+// are read coalesced, the two header bytes only for a packet that verified (so always inside it).
+// Each workgroup leaves its count of eligible packets in blk[] (phase 2 compacts with it) and adds
+// it to tot[0]; the workgroup that takes the last ticket (tot[1]) stores the batch's count into the
+// pinned host word the caller reads after its stream synchronize (rx_final_window_kernel's
+// need_host pattern) and zeroes both words for the next batch. Every thread reaches the barriers.
+__global__ __launch_bounds__(256) void rx_via_unwrap_kernel(const int32_t* __restrict__ gate, int32_t* __restrict__ status,
+                                                            const neb_rx_packet* __restrict__ pk,
+                                                            const neb_rx_via* __restrict__ via, uint32_t n,
+                                                            const uint8_t* __restrict__ arena,
+                                                            neb_rx_packet* __restrict__ inner_pk,
+                                                            int32_t* __restrict__ inner_status, uint32_t* __restrict__ blk,
+                                                            uint32_t* tot, uint32_t* h_count) {
+    __shared__ uint32_t s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool eligible = false;
+    if (i < n) {
+        const int32_t g = gate[i];
+        int32_t st = status[i];
+        if (g != NEB_STATUS_OK) status[i] = st = g;
+        const neb_rx_packet p = pk[i];
+        const neb_rx_via v = via[i];
+        uint8_t h0 = 0, h1 = 0;
+        if (st == NEB_STATUS_OK) {
+            h0 = arena[p.off];
+            h1 = arena[p.off + 1u];
+        }
+        neb_rx_packet in;
+        eligible = neb_rx_via_unwrap(st, h0, h1, p, v, &in);
+        inner_pk[i] = in;
+        inner_status[i] = eligible ? NEB_STATUS_OK : NEB_STATUS_NOT_RELAYED;
+    }
+    const unsigned long long m = __ballot(eligible);
+    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_cnt, (uint32_t)__popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = s_cnt;
+        atomicAdd(&tot[0], s_cnt);
+        __threadfence();
+        if (atomicAdd(&tot[1], 1u) == gridDim.x - 1u) {  // the last workgroup: every count is in
+            __threadfence();
+            *h_count = atomicExch(&tot[0], 0u);
+            atomicExch(&tot[1], 0u);
+        }
+    }
+}
+
+// rx_wire_kernel over the inner records of neb_rx_open_via_batch, compacted: the eligible records
+// (the ones the unwrap did not mark NEB_STATUS_NOT_RELAYED) keep their arrival order, the j-th of
+// them gets descriptor j, gate status j and map[j] = its index. Its place is the eligible count of
+// the workgroups before its own (blk[], summed by the whole workgroup) plus its rank inside the
+// workgroup (a ballot per wave). The gate runs with relayed = true. m: the batch's eligible count.
+__global__ __launch_bounds__(256) void rx_wire_inner_kernel(const neb_rx_packet* __restrict__ pk,
+                                                            const int32_t* __restrict__ inner_status, uint32_t n,
+                                                            const uint8_t* __restrict__ arena,
+                                                            const uint32_t* __restrict__ blk, uint32_t m,
+                                                            neb_desc* __restrict__ desc, int32_t* __restrict__ gate,
+                                                            uint32_t* __restrict__ map) {
+    __shared__ uint32_t s_base, s_wave[4];
+    if (threadIdx.x == 0) s_base = 0;
+    __syncthreads();
+    uint32_t part = 0;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 256u) part += blk[b];
+    if (part) atomicAdd(&s_base, part);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool el = i < n && inner_status[i] != NEB_STATUS_NOT_RELAYED;
+    const unsigned long long bal = __ballot(el);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    if (!el) return;
+    uint32_t pos = s_base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wave; w++) pos += s_wave[w];
+    if (pos >= m) return;  // (cannot happen: m is the sum of blk[])
+    const neb_rx_packet p = pk[i];
+    uint8_t h[16];
+    if (neb_rx_len(p) >= 16u)
+        for (int k = 0; k < 16; k++) h[k] = arena[p.off + k];
+    neb_desc d{p.off, p.off, p.off, 0, 0, 0, NEB_KEYS_MIXED, 0};
+    const int32_t g = neb_rx_wire_gate(h, p, &d, true);
+    if (g != NEB_STATUS_OK) d = neb_desc{p.off, p.off, p.off, 0, 0, 0, NEB_KEYS_MIXED, 0};
+    desc[pos] = d;
+    gate[pos] = g;
+    map[pos] = i;
+}
+
+// inner_status of the j-th eligible packet: the gate's status where it refused the packet, else
+// what the receive gave the compacted batch
+__global__ __launch_bounds__(256) void rx_via_fix_kernel(const int32_t* __restrict__ gate, const int32_t* __restrict__ sub,
+                                                         const uint32_t* __restrict__ map, uint32_t m,
+                                                         int32_t* __restrict__ inner_status) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < m) inner_status[map[j]] = gate[j] != NEB_STATUS_OK ? gate[j] : sub[j];
+}
+
 __device__ __forceinline__ bool rx_fast(uint32_t fl) { return (fl & kRxTouched) && !(fl & (kRxRisky | kRxSlow)); }
 
 // Per admitted packet, in run order (the windows' runs are contiguous there, so the atomics below
@@ -800,6 +898,33 @@ extern "C" hipError_t neb_rxdev_wire(const neb_rx_packet* d_pk, uint32_t n, cons
 extern "C" hipError_t neb_rxdev_wire_fix(const int32_t* d_gate, int32_t* d_status, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(neb::rx_wire_fix_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d_gate, d_status, n);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t neb_rxdev_via_unwrap(const int32_t* d_gate, int32_t* d_status, const neb_rx_packet* d_pk,
+                                           const neb_rx_via* d_via, uint32_t n, const uint8_t* d_arena,
+                                           neb_rx_packet* d_inner_pk, int32_t* d_inner_status, uint32_t* d_blk,
+                                           uint32_t* d_tot, uint32_t* h_count, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(neb::rx_via_unwrap_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d_gate, d_status, d_pk, d_via,
+                       n, d_arena, d_inner_pk, d_inner_status, d_blk, d_tot, h_count);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t neb_rxdev_wire_inner(const neb_rx_packet* d_inner_pk, const int32_t* d_inner_status, uint32_t n,
+                                           const uint8_t* d_arena, const uint32_t* d_blk, uint32_t m, neb_desc* d_desc,
+                                           int32_t* d_gate, uint32_t* d_map, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(neb::rx_wire_inner_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d_inner_pk, d_inner_status,
+                       n, d_arena, d_blk, m, d_desc, d_gate, d_map);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t neb_rxdev_via_fix(const int32_t* d_gate, const int32_t* d_sub, const uint32_t* d_map, uint32_t m,
+                                        int32_t* d_inner_status, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(neb::rx_via_fix_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, d_gate, d_sub, d_map, m,
+                       d_inner_status);
     return hipGetLastError();
 }
 

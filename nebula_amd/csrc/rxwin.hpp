@@ -159,7 +159,11 @@ extern "C" hipError_t neb_rxdev_gather(const neb_desc* d_desc, uint32_t n, const
 // over packet[:len-16]), or the status the packet ends with. h: the first 16 bytes (read only when
 // len >= 16). Shared by the host (window.cpp) and the device (rx_wire_kernel) forms.
 __host__ __device__ inline uint32_t neb_rx_len(const neb_rx_packet& p) { return p.len & ~NEB_RX_OWN_SOURCE; }
-__host__ __device__ inline int32_t neb_rx_wire_gate(const uint8_t* h, const neb_rx_packet& p, neb_desc* d) {
+// relayed: the packet came out of a terminal relay packet (IsRelayed). An inner Message/Relay is
+// then left to the caller, NEB_STATUS_NOT_MESSAGE, where the unencrypted types are handed over:
+// one level of handleOutsideRelayPacket's recursion per call (neb_rx_open_via_batch).
+__host__ __device__ inline int32_t neb_rx_wire_gate(const uint8_t* h, const neb_rx_packet& p, neb_desc* d,
+                                                    bool relayed = false) {
     const uint32_t len = neb_rx_len(p);
     if (len < 16u) return NEB_STATUS_INVALID;  // h.Parse: ErrHeaderTooShort (header.go:144-146)
     const uint32_t ver = h[0] >> 4, type = h[0] & 15u, sub = h[1];
@@ -172,6 +176,7 @@ __host__ __device__ inline int32_t neb_rx_wire_gate(const uint8_t* h, const neb_
     // node's own VPN networks), which needs the source address the batch does not carry
     if (p.len & NEB_RX_OWN_SOURCE) return NEB_STATUS_INVALID;
     if (type == 0u || type == 2u) return NEB_STATUS_NOT_MESSAGE;  // handshake, recv error (outside.go:83-89)
+    if (relayed && type == 1u && sub == 1u) return NEB_STATUS_NOT_MESSAGE;  // a relay inside a relay: the caller's
     if (p.key_id == NEB_KEYS_MIXED) return NEB_STATUS_BAD_KEY;    // no hostinfo (outside.go:100-106)
     if (len < 32u) return NEB_STATUS_INVALID;                     // header.Len + Overhead (outside.go:108-114)
     uint64_t c = 0;
@@ -192,6 +197,19 @@ __host__ __device__ inline int32_t neb_rx_wire_gate(const uint8_t* h, const neb_
     return NEB_STATUS_OK;
 }
 
+// handleOutsideRelayPacket's TerminalType branch (outside.go:210-219) for one finished outer packet:
+// true with *inner = packet[16 : len-16] under the caller's inner tunnel when the packet is a
+// verified Message/Relay for this node, else false with an empty record. h0, h1: the first two
+// header bytes (read by the caller only when status is NEB_STATUS_OK, which implies len >= 32).
+// Shared by neb_rx_via_unwrap_host, the host form and rx_via_unwrap_kernel.
+__host__ __device__ inline bool neb_rx_via_unwrap(int32_t status, uint8_t h0, uint8_t h1, const neb_rx_packet& p,
+                                                  const neb_rx_via& v, neb_rx_packet* inner) {
+    const bool eligible =
+        status == NEB_STATUS_OK && (h0 & 15u) == 1u && h1 == 1u && (v.flags & NEB_VIA_TERMINAL) && neb_rx_len(p) >= 32u;
+    *inner = eligible ? neb_rx_packet{p.off + 16u, neb_rx_len(p) - 32u, v.key_id} : neb_rx_packet{p.off, 0u, NEB_KEYS_MIXED};
+    return eligible;
+}
+
 // Byte spans between two device buffers, one wave per span (the exact receive pass's speculative
 // opens: packets copied out of the arena into a scratch buffer, plaintext copied back for the ones
 // the windows accept, zeros for the ones that pass their window but fail their tag). src == NULL
@@ -208,6 +226,22 @@ extern "C" hipError_t neb_rxdev_wire(const neb_rx_packet* d_pk, uint32_t n, cons
                                      int32_t* d_gate, hipStream_t s);
 // status[i] = gate[i] wherever the gate refused the packet
 extern "C" hipError_t neb_rxdev_wire_fix(const int32_t* d_gate, int32_t* d_status, uint32_t n, hipStream_t s);
+// neb_rx_open_via_batch, in place of neb_rxdev_wire_fix: the same status fix, then the unwrap rule
+// per packet (inner_pk, and inner_status = NEB_STATUS_NOT_RELAYED or, for a packet phase 2 will
+// run, NEB_STATUS_OK). d_blk: the eligible count of every workgroup of 256 packets; d_tot: two
+// words, zero between batches; *h_count (a pinned host word): the batch's eligible count
+extern "C" hipError_t neb_rxdev_via_unwrap(const int32_t* d_gate, int32_t* d_status, const neb_rx_packet* d_pk,
+                                           const neb_rx_via* d_via, uint32_t n, const uint8_t* d_arena,
+                                           neb_rx_packet* d_inner_pk, int32_t* d_inner_status, uint32_t* d_blk,
+                                           uint32_t* d_tot, uint32_t* h_count, hipStream_t s);
+// neb_rxdev_wire over the m eligible inner records, compacted in arrival order (the gate with
+// relayed = true): descriptor, gate status and arrival index (d_map) of the j-th of them
+extern "C" hipError_t neb_rxdev_wire_inner(const neb_rx_packet* d_inner_pk, const int32_t* d_inner_status, uint32_t n,
+                                           const uint8_t* d_arena, const uint32_t* d_blk, uint32_t m, neb_desc* d_desc,
+                                           int32_t* d_gate, uint32_t* d_map, hipStream_t s);
+// inner_status[d_map[j]] = the gate's status where it refused the packet, else d_sub[j]
+extern "C" hipError_t neb_rxdev_via_fix(const int32_t* d_gate, const int32_t* d_sub, const uint32_t* d_map, uint32_t m,
+                                        int32_t* d_inner_status, hipStream_t s);
 // After the open (which ran the admitted packets only, ws->adm, writing their statuses): verdicts,
 // the admitted counters into the windows, and the finish of every window whose packets all verified.
 extern "C" hipError_t neb_rxdev_finish(uint32_t n, const neb::RxDevWin* win, const neb::RxDevWs* ws,

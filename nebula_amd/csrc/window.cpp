@@ -360,7 +360,9 @@ struct neb_dwindows {
     neb::RxDevWs ws{};
     uint32_t ws_n = 0;
     uint32_t* h_host = nullptr;  // pinned, mapped, 2 words (RxDevWs::need_host): a window needs the host; the scan failed
-    uint8_t* wire_mem = nullptr;  // neb_rx_open_wire_batch: descriptors + gate statuses
+    // neb_rx_open_wire_batch: descriptors + gate statuses; then neb_rx_open_via_batch's compaction
+    // (WireMem below): arrival indices, compacted statuses, per-workgroup counts, two counter words
+    uint8_t* wire_mem = nullptr;
     uint32_t wire_n = 0;
     uint32_t spin_limit = neb::kRxSpinLimit;  // neb_dwindows_set_spin_limit
     SchedSpace* sched = nullptr;  // mixed-key AES-GCM receives: the open's scheduler workspace (rxwin.hpp RxBin)
@@ -370,6 +372,8 @@ struct neb_dwindows {
     neb::RelayWs relay_ws{};
     uint32_t relay_n = 0, relay_tun = 0;
     uint32_t* relay_key = nullptr;
+    // neb_rx_open_via_batch: one pinned, mapped word, the unwrap kernel's count of inner packets
+    uint32_t* via_count = nullptr;
 };
 
 namespace {
@@ -471,6 +475,7 @@ NEB_API int neb_dwindows_destroy(neb_dwindows* d) {
         neb_sched_space_free(d->sched);
         d->relay.destroy();  // (waits: the forward half of the last relay batch may still be running)
         if (d->relay_key) hipHostFree(d->relay_key);
+        if (d->via_count) hipHostFree(d->via_count);
         if (d->ws_mem) hipFree(d->ws_mem);
         if (d->wire_mem) hipFree(d->wire_mem);
         if (d->mem) hipFree(d->mem);
@@ -743,6 +748,10 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
     return NEB_OK;
 }
 
+static int rx_open_wire_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                             const neb_rx_packet* pk, uint32_t n, uint8_t* arena, size_t arena_len, int32_t* status,
+                             uint32_t key_hint, bool relayed);
+
 extern "C" {
 
 NEB_API int neb_rx_open_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_desc* d_desc, uint32_t n,
@@ -762,6 +771,17 @@ NEB_API int neb_rx_open_batch(neb_engine* e, int alg, neb_dwindows* d, const neb
 NEB_API int neb_rx_open_wire_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
                                         const neb_rx_packet* pk, uint32_t n, uint8_t* arena, size_t arena_len,
                                         int32_t* status, uint32_t key_hint) {
+    return rx_open_wire_host(e, alg, windows, nwindows, pk, n, arena, arena_len, status, key_hint, false);
+}
+
+}  // extern "C"
+
+// relayed: pk are the inner records of neb_rx_open_via_batch_host and status[] holds the unwrap's
+// marks: a record marked NEB_STATUS_NOT_RELAYED keeps that status, the others pass the gate with
+// relayed = true.
+static int rx_open_wire_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                             const neb_rx_packet* pk, uint32_t n, uint8_t* arena, size_t arena_len, int32_t* status,
+                             uint32_t key_hint, bool relayed) {
     if (!e || (n && (!pk || !arena || !status || !windows))) return NEB_ERR_INVALID;
     if (n == 0) return NEB_OK;
     for (uint32_t i = 0; i < n; i++)  // every wire packet inside the arena (sums cannot wrap)
@@ -770,7 +790,8 @@ NEB_API int neb_rx_open_wire_batch_host(neb_engine* e, int alg, neb_window* cons
     std::vector<int32_t> gate(n);
     for (uint32_t i = 0; i < n; i++) {
         neb_desc dd{pk[i].off, pk[i].off, pk[i].off, 0, 0, 0, NEB_KEYS_MIXED, 0};
-        gate[i] = neb_rx_wire_gate(arena + pk[i].off, pk[i], &dd);
+        gate[i] = relayed && status[i] == NEB_STATUS_NOT_RELAYED ? NEB_STATUS_NOT_RELAYED
+                                                                 : neb_rx_wire_gate(arena + pk[i].off, pk[i], &dd, relayed);
         if (gate[i] != NEB_STATUS_OK) dd = neb_desc{pk[i].off, pk[i].off, pk[i].off, 0, 0, 0, NEB_KEYS_MIXED, 0};
         desc[i] = dd;
     }
@@ -781,12 +802,36 @@ NEB_API int neb_rx_open_wire_batch_host(neb_engine* e, int alg, neb_window* cons
     return NEB_OK;
 }
 
-}  // extern "C"
+// d->wire_mem carved for a capacity of n packets: the wire receive's descriptors and gate statuses,
+// then what neb_rx_open_via_batch's compacted phase 2 adds (the compacted batch's statuses and
+// arrival indices, the unwrap kernel's per-workgroup counts and its two counter words)
+struct WireMem {
+    neb_desc* desc;
+    int32_t *gate, *sub;
+    uint32_t *map, *blk, *tot;
+    static size_t bytes(uint32_t n) { return (size_t)n * (sizeof(neb_desc) + 12) + ((size_t)(n + 255u) / 256u + 2) * 4; }
+    WireMem(uint8_t* m, uint32_t n) {
+        desc = (neb_desc*)m;
+        gate = (int32_t*)(desc + n);
+        sub = gate + n;
+        map = (uint32_t*)(sub + n);
+        blk = map + n;
+        tot = blk + ((size_t)n + 255u) / 256u;
+    }
+};
+struct RxViaArgs {  // neb_rx_open_via_batch's arrays for the unwrap
+    const neb_rx_via* d_via;
+    neb_rx_packet* d_inner_pk;
+    int32_t* d_inner_status;
+};
 
 // neb_rx_open_wire_batch with d->mu held and the engine's device current (the relay forwarding runs
-// its forward half under the same lock)
+// its forward half under the same lock). via: the unwrap of neb_rx_open_via_batch runs in place of
+// the status fix (one kernel for both), and its count, in the pinned word d->via_count, arrives
+// with the synchronize that ends the receive.
 static int rx_open_wire_locked(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk, uint32_t n,
-                               uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
+                               uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream,
+                               const RxViaArgs* via = nullptr) {
     int rc = NEB_OK;
     hipStream_t s = (hipStream_t)stream;
     if (n > d->wire_n) {
@@ -794,15 +839,21 @@ static int rx_open_wire_locked(neb_engine* e, int alg, neb_dwindows* d, const ne
         if (d->wire_mem) hipFree(d->wire_mem);
         d->wire_mem = nullptr;
         d->wire_n = 0;
-        RX_HIP(hipMalloc((void**)&d->wire_mem, (size_t)n * (sizeof(neb_desc) + 4)));
+        RX_HIP(hipMalloc((void**)&d->wire_mem, WireMem::bytes(n)));
         d->wire_n = n;
+        RX_HIP(hipMemsetAsync(WireMem(d->wire_mem, n).tot, 0, 8, s));  // zero between batches from here on
     }
-    neb_desc* wd = (neb_desc*)d->wire_mem;
-    int32_t* gate = (int32_t*)(d->wire_mem + (size_t)d->wire_n * sizeof(neb_desc));
+    const WireMem wm(d->wire_mem, d->wire_n);
+    neb_desc* wd = wm.desc;
+    int32_t* gate = wm.gate;
     RX_HIP(neb_rxdev_wire(d_pk, n, d_arena, wd, gate, s));
     rc = rx_open_batch_locked(e, alg, d, wd, n, d_arena, d_status, key_hint, stream);
     if (rc != NEB_OK) return rc;
-    RX_HIP(neb_rxdev_wire_fix(gate, d_status, n, s));
+    if (via)
+        RX_HIP(neb_rxdev_via_unwrap(gate, d_status, d_pk, via->d_via, n, d_arena, via->d_inner_pk, via->d_inner_status,
+                                    wm.blk, wm.tot, d->via_count, s));
+    else
+        RX_HIP(neb_rxdev_wire_fix(gate, d_status, n, s));
     RX_HIP(hipStreamSynchronize(s));
     return NEB_OK;
 }
@@ -906,6 +957,71 @@ NEB_API int neb_relay_forward_batch_host(neb_engine* e, int alg, neb_window* con
     if (rc != NEB_OK) return rc;
     for (size_t j = 0; j < sub.size(); j++)
         if (sub[j] != NEB_STATUS_OK) fwd_status[map[j]] = sub[j];
+    return NEB_OK;
+}
+
+}  // extern "C"
+
+// ---- receive through a relay: VerifyRelay, then unwrap and open (rxwin.hpp neb_rx_via_unwrap) -----
+
+extern "C" {
+
+NEB_API int neb_rx_via_unwrap_host(const neb_rx_packet* pk, const neb_rx_via* via, const int32_t* status, uint32_t n,
+                                   const uint8_t* arena, size_t arena_len, neb_rx_packet* inner_pk,
+                                   int32_t* inner_status) {
+    if (n && (!pk || !via || !status || !arena || !inner_pk || !inner_status)) return NEB_ERR_INVALID;
+    for (uint32_t i = 0; i < n; i++)
+        if (pk[i].off > arena_len || neb_rx_len(pk[i]) > arena_len - pk[i].off) return NEB_ERR_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool ok = status[i] == NEB_STATUS_OK && neb_rx_len(pk[i]) >= 2u;
+        const uint8_t* h = arena + pk[i].off;
+        const bool el = neb_rx_via_unwrap(status[i], ok ? h[0] : 0, ok ? h[1] : 0, pk[i], via[i], &inner_pk[i]);
+        inner_status[i] = el ? NEB_STATUS_OK : NEB_STATUS_NOT_RELAYED;
+    }
+    return NEB_OK;
+}
+
+NEB_API int neb_rx_open_via_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                                       const neb_rx_packet* pk, const neb_rx_via* via, uint32_t n, uint8_t* arena,
+                                       size_t arena_len, int32_t* status, neb_rx_packet* inner_pk,
+                                       int32_t* inner_status, uint32_t key_hint, uint32_t inner_key_hint) {
+    if (!e || (n && (!via || !inner_pk || !inner_status))) return NEB_ERR_INVALID;
+    int rc = neb_rx_open_wire_batch_host(e, alg, windows, nwindows, pk, n, arena, arena_len, status, key_hint);
+    if (rc != NEB_OK || n == 0) return rc;
+    if ((rc = neb_rx_via_unwrap_host(pk, via, status, n, arena, arena_len, inner_pk, inner_status)) != NEB_OK) return rc;
+    bool any = false;
+    for (uint32_t i = 0; i < n && !any; i++) any = inner_status[i] != NEB_STATUS_NOT_RELAYED;
+    if (!any) return NEB_OK;
+    return rx_open_wire_host(e, alg, windows, nwindows, inner_pk, n, arena, arena_len, inner_status, inner_key_hint, true);
+}
+
+NEB_API int neb_rx_open_via_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_rx_packet* d_pk,
+                                  const neb_rx_via* d_via, uint32_t n, uint8_t* d_arena, int32_t* d_status,
+                                  neb_rx_packet* d_inner_pk, int32_t* d_inner_status, uint32_t key_hint,
+                                  uint32_t inner_key_hint, void* stream) {
+    if (!e || !d || d->e != e || (n && (!d_pk || !d_via || !d_arena || !d_status || !d_inner_pk || !d_inner_status)))
+        return NEB_ERR_INVALID;
+    int rc = neb_check_batch_args(e, alg, key_hint);
+    if (rc == NEB_OK) rc = neb_check_batch_args(e, alg, inner_key_hint);
+    if (rc != NEB_OK) return rc;
+    if (n == 0) return NEB_OK;
+    std::lock_guard<std::mutex> g(d->mu);
+    DeviceGuard dg(neb_engine_device_of(e));
+    hipStream_t s = (hipStream_t)stream;
+    if (!d->via_count) RX_HIP(hipHostMalloc((void**)&d->via_count, sizeof(uint32_t), hipHostMallocMapped));
+    *d->via_count = 0;
+    const RxViaArgs via{d_via, d_inner_pk, d_inner_status};
+    if ((rc = rx_open_wire_locked(e, alg, d, d_pk, n, d_arena, d_status, key_hint, stream, &via)) != NEB_OK) return rc;
+    // no terminal relay packet verified: every inner_status is NEB_STATUS_NOT_RELAYED already
+    const uint32_t m = __atomic_load_n(d->via_count, __ATOMIC_ACQUIRE);
+    if (m == 0) return NEB_OK;
+    if (m > n) return NEB_ERR_HIP;
+    // phase 2 over the m inner packets, compacted in arrival order; phase 1 is done with wire_mem
+    const WireMem wm(d->wire_mem, d->wire_n);
+    RX_HIP(neb_rxdev_wire_inner(d_inner_pk, d_inner_status, n, d_arena, wm.blk, m, wm.desc, wm.gate, wm.map, s));
+    if ((rc = rx_open_batch_locked(e, alg, d, wm.desc, m, d_arena, wm.sub, inner_key_hint, stream)) != NEB_OK) return rc;
+    RX_HIP(neb_rxdev_via_fix(wm.gate, wm.sub, wm.map, m, d_inner_status, s));
+    RX_HIP(hipStreamSynchronize(s));
     return NEB_OK;
 }
 
