@@ -1027,6 +1027,8 @@ __device__ __forceinline__ void gcm_packet_group(const GcmArgs& args, uint32_t p
     sh.R = run ? (sh.n + LPP - 1u) >> lg : 0u;
     sh.pad = (sh.R << lg) - sh.n;
     Ej0Reg ej0;
+    // the uniform-round loop (below): the single-key kernel's plain seal and open only
+    constexpr bool kUni = std::is_same_v<GH, GhFullPerm> && !CS && !RX;
 
     // nonce 00000000 || BE64(n) as little-endian words; counter block word 3 = BE32(ctr)
     const uint32_t c1 = bswap32((uint32_t)(d.counter >> 32));
@@ -1106,6 +1108,58 @@ __device__ __forceinline__ void gcm_packet_group(const GcmArgs& args, uint32_t p
             }
             NEB_MARK(round_end);
         };
+        // Uniform waves (single-key kernel, counter tier 2, plain seal and open): when all 16 packets
+        // run with one (aad_len, len), no header bytes from the destination, 16-B aligned destinations
+        // and 4-B aligned sources, a round's block roles depend on (r, l) alone. The rounds [u0, u1)
+        // in which every lane holds a full payload block then run with a scalar trip count, one
+        // running source and destination pointer per lane and ctr += 4: no roles, votes, alignment
+        // tests or address rebuilds. The rounds before (AAD, pad) and after (partial block, length
+        // block, E_K(J0)) stay with tround. One test per wave; any other wave runs the general loop,
+        // which is a loop of its own: entered from inside it, the uniform rounds changed its
+        // register allocation and cost the 1-key relay (AAD-only rounds) 6%.
+        if constexpr (kUni && CM == 2) {
+            uint32_t u0 = ~0u, u1 = 0u;
+            const uint32_t ulen = __builtin_amdgcn_readfirstlane(d.len);
+            const uint32_t uaad = __builtin_amdgcn_readfirstlane(d.aad_len);
+            const uintptr_t ab = reinterpret_cast<uintptr_t>(args.arena);
+            if (__all(run && d.len == ulen && d.aad_len == uaad && hdr == 0u &&
+                      (((uint32_t)d.dst_off | (uint32_t)ab) & 15u) == 0u &&
+                      (((uint32_t)d.src_off + (uint32_t)ab) & 3u) == 0u)) {
+                const uint32_t na = (uaad + 15u) >> 4, n = na + ((ulen + 15u) >> 4) + 1u;
+                const uint32_t pad = (((n + LPP - 1u) >> lg) << lg) - n;
+                const uint32_t a = (na + pad + LPP - 1u) >> lg, b = (na + pad + (ulen >> 4)) >> lg;
+                if (a < b) u0 = a, u1 = b;
+            }
+            if (u0 != ~0u) {
+                // tround over [0, u0), the uniform rounds [u0, u1), tround over [u1, R): written as
+                // one loop that jumps from u0 to u1, so that tround is inlined once here and not twice
+                const uint32_t uR = __builtin_amdgcn_readfirstlane(sh.R);
+                for (uint32_t r = 0; r < uR; r++) {
+                    if (r == u0) {
+                        const uint32_t k0 = (u0 << lg) + l + 1u - sh.pad - sh.na;  // this lane's first block
+                        const uint8_t* sp = args.arena + d.src_off + 16u * (k0 - 1u);
+                        uint8_t* dp = args.arena + d.dst_off + 16u * (k0 - 1u);
+                        uint32_t ctr = k0 + 1u;
+                        for (uint32_t i = u0; i < u1; i++) {
+                            NEB_MARK(uround_begin);
+                            const uint4 in = load_u4_a4(sp);
+                            const uint4 G = gh.horner(A, lg);
+                            __builtin_amdgcn_sched_barrier(0);
+                            const uint4 out = xor4(in, aes256_ctr8_block(cc, ctr, T, rk));
+                            *reinterpret_cast<uint4*>(dp) = out;
+                            A = xor4(G, bswap4(OPEN ? in : out));
+                            sp += 16u * LPP;
+                            dp += 16u * LPP;
+                            ctr += LPP;
+                            NEB_MARK(uround_end);
+                        }
+                        r = u1;
+                    }
+                    tround(r);
+                }
+                return;
+            }
+        }
         // rounds until no packet of the wave has one left (a ballot, no cross-lane reduction; a
         // shuffle max of the round counts first was 4-7% slower in the chunk kernel)
         for (uint32_t r = 0; __any(r < sh.R); r++) tround(r);
