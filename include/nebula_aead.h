@@ -48,6 +48,11 @@
  *                            virtio header of every TUN write (overlay/tio/tio_gso_linux.go:280-404);
  *                            neb_rx_plain_from_wire is handleOutsideMessagePacket's hand-over
  *                            (outside.go:145-149, :474-479)
+ *   neb_rx_resolve_batch     the lookups readOutsidePackets makes per datagram before it decrypts:
+ *                            myVpnNetworksTable.Contains (outside.go:66-74), QueryIndexCached /
+ *                            QueryRelayIndex (outside.go:93-106, hostmap.go:546-577) and
+ *                            handleOutsideRelayPacket's QueryRelayForByIdx / QueryVpnAddrsRelayFor
+ *                            (outside.go:201-240), over neb_index_table_*
  *   neb_queue_*              the flush points themselves (flushSendBatch interface.go:478-487,
  *                            listenOut's flush :395-400) of every routine (interface.go:320-335),
  *                            gathered into shared device batches
@@ -661,6 +666,88 @@ NEB_API int neb_rx_plain_from_wire(neb_engine* e, const neb_rx_packet* d_pk, con
 NEB_API int neb_rx_plain_from_wire_host(const neb_rx_packet* pk, const int32_t* status, const uint64_t* epoch,
                                         uint32_t nepoch, uint32_t n, const uint8_t* arena, size_t arena_len,
                                         neb_plain_packet* plain);
+/* ---- receive resolve: the hostmap's index lookups for a whole receive batch ---------------------- */
+/* What readOutsidePackets looks up per datagram before it can decrypt: the tunnel of the header's
+ * remote index (hostMap.QueryIndexCached / QueryRelayIndex, outside.go:93-100, hostmap.go:546-577),
+ * the double-encryption check on the UDP source (f.myVpnNetworksTable.Contains, outside.go:66-74),
+ * and, for Message/Relay, the relay's type and target (relayState.QueryRelayForByIdx,
+ * QueryVpnAddrsRelayFor, outside.go:201-240). Each is a pure function of a 32-bit local index or of
+ * an address over state that changes only at handshakes and relay set-up, so the state lives in a
+ * table beside the keys and the windows, and one call fills neb_rx_packet.key_id,
+ * NEB_RX_OWN_SOURCE, neb_relay_route and neb_rx_via for the calls above. */
+#define NEB_INDEX_TUNNEL 0 /* hostMap.Indexes (hostmap.go:60, :669) */
+#define NEB_INDEX_RELAY 1  /* hostMap.Relays  (hostmap.go:61) */
+#define NEB_INDEX_MAX_NETWORKS 16
+typedef struct neb_index_key {
+    uint32_t index, space;
+} neb_index_key;
+typedef struct neb_index_entry {
+    uint32_t index, space;
+    uint32_t key_id;       /* the HostInfo's window / key slot; NEB_KEYS_MIXED: ConnectionState == nil */
+    uint32_t flags;        /* relay space: NEB_VIA_TERMINAL for a TerminalType relay index */
+    neb_relay_route route; /* relay space: the Established ForwardingType target, else {NEB_RELAY_NONE, 0} */
+} neb_index_entry;
+typedef struct neb_cidr { /* one of the node's own VPN networks (pki.go:477) */
+    uint8_t addr[16];     /* family 4: the first 4 bytes */
+    uint8_t family /* 4 | 6 */, bits, reserved[2];
+} neb_cidr;
+typedef struct neb_rx_source { /* the UDP source of a datagram, unmapped (udp/udp_linux.go:245) */
+    uint8_t addr[16];          /* family 4: the first 4 bytes, the rest is ignored */
+    uint8_t family /* 0 none, 4, 6 */, reserved[3];
+} neb_rx_source;
+typedef struct neb_index_table neb_index_table;
+
+/* A table of at most `capacity` live entries (fixed; capacity >= 1). e == NULL: a host-only table
+ * (neb_rx_resolve_batch_host only); otherwise the table also keeps its image in e's device memory. */
+NEB_API int neb_index_table_create(neb_engine* e, uint32_t capacity, neb_index_table** out);
+/* No call on the table may be in progress; waits for the device work the table has enqueued. */
+NEB_API int neb_index_table_destroy(neb_index_table* t);
+/* The deletions in array order, then the puts in array order. A put of a live key replaces its
+ * record; deleting an absent key is not an error. NEB_ERR_INVALID (nothing applied): space > 1, or
+ * a tunnel-space entry with flags != 0 or route.tunnel != NEB_RELAY_NONE. NEB_ERR_NO_KEY_SLOT
+ * (nothing applied): more than `capacity` entries would be live after the call. Thread-safe.
+ * Visibility of the device image: a resolve enqueued on `stream` after this call sees the update. A
+ * resolve running on another stream meanwhile sees, for every key, its record from before or from
+ * after this call, never a mix, and never a miss for a key that is live before and after. Updates
+ * given on different streams take effect in the order of the calls. The call returns once its work
+ * is enqueued, except when the table compacts itself (its deleted and replaced records have filled
+ * 3/4 of its slots): it then waits for every resolve that still reads the spare image, writes that
+ * image, waits for `stream`, and switches over, so it may block the calling control-plane thread
+ * for as long as those batches take. stream is ignored by a host-only table. */
+NEB_API int neb_index_table_update(neb_index_table* t, const neb_index_key* del, uint32_t ndel,
+                                   const neb_index_entry* put, uint32_t nput, void* stream);
+/* Replaces the node's own networks (at most NEB_INDEX_MAX_NETWORKS; NEB_ERR_INVALID: more, a family
+ * other than 4 / 6, or bits beyond the family's width). Matching is netip.Prefix.Contains: a 4-byte
+ * address against the v4 prefixes only, a 16-byte address, 4-in-6 included, against the v6 prefixes
+ * only. Resolves called after this returns use the new set; stream is not used. */
+NEB_API int neb_index_table_set_own_networks(neb_index_table* t, const neb_cidr* nets, uint32_t n, void* stream);
+NEB_API int neb_index_table_count(const neb_index_table* t, uint32_t* live);
+/* For tests, from the host copy: out = {found, slot, probes}: the slot of the key (found) or the
+ * empty slot that ended the search, and the slots examined. */
+NEB_API int neb_index_table_probe(const neb_index_table* t, uint32_t space, uint32_t index, uint32_t out[3]);
+/* Per packet i, with len = pk[i].len without NEB_RX_OWN_SOURCE; off and len are the caller's:
+ *   key = NEB_KEYS_MIXED, route = {NEB_RELAY_NONE, 0}, via = {NEB_KEYS_MIXED, 0};
+ *   src given, src[i].family != 0 and the own networks contain src[i]: pk[i].len |= NEB_RX_OWN_SOURCE
+ *   (the bit is never cleared);
+ *   len >= 16: relay = (h[0] & 15) == 1 && h[1] == 1 for the header h at off, idx = BE32(h[4:8]);
+ *   the entry of (relay ? NEB_INDEX_RELAY : NEB_INDEX_TUNNEL, idx), if any, gives key = key_id and,
+ *   when relay: route = its route if route.tunnel != NEB_RELAY_NONE; if flags & NEB_VIA_TERMINAL,
+ *   via.flags = NEB_VIA_TERMINAL and, when len >= 48, via.key_id = the key_id of the entry the
+ *   header at off + 16 names the same way (its own relay bit chooses the space).
+ * Every packet of 16 bytes or more is looked up, whatever its version and type: the drops and their
+ * order stay with the receive calls' gate. Writes pk[i].key_id, the flag bit, route[i] and via[i]
+ * (each array may be NULL: not written) and nothing else. n == 0 returns NEB_OK. The call only
+ * enqueues one kernel on `stream`, in front of neb_rx_open_wire_batch / neb_relay_forward_batch /
+ * neb_rx_open_via_batch on the same stream; d_src is 4-byte aligned. The caller reads pk[i].key_id
+ * back together with status[i]. NEB_ERR_INVALID for a host-only table. */
+NEB_API int neb_rx_resolve_batch(neb_engine* e, const neb_index_table* t, neb_rx_packet* d_pk,
+                                 const neb_rx_source* d_src, uint32_t n, const uint8_t* d_arena,
+                                 neb_relay_route* d_route, neb_rx_via* d_via, void* stream);
+/* The same over host memory, from the table's host copy (any table). Every pk is checked against
+ * arena_len first (NEB_ERR_INVALID: nothing written). */
+NEB_API int neb_rx_resolve_batch_host(const neb_index_table* t, neb_rx_packet* pk, const neb_rx_source* src,
+                                      uint32_t n, const uint8_t* arena, size_t arena_len, neb_relay_route* route,
+                                      neb_rx_via* via);
 /* ---- submission queue: many threads' small flushes -> device-sized batches -------------------- */
 /* Nebula seals <= 128 packets per TX flush (overlay/batch/tx_batch.go:5, flushSendBatch
  * interface.go:465-487) and opens <= listen.batch = 64 per RX flush (main.go:181, listenOut

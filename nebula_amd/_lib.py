@@ -68,6 +68,16 @@ assert RELAY_ROUTE_DTYPE.itemsize == 8
 # neb_rx_via (include/nebula_aead.h): the caller's lookups for the packet inside a relay packet
 RX_VIA_DTYPE = np.dtype([("key_id", "<u4"), ("flags", "<u4")])
 assert RX_VIA_DTYPE.itemsize == 8
+# neb_index_table_* (include/nebula_aead.h): the hostmap's receive-side index lookups
+INDEX_TUNNEL, INDEX_RELAY = 0, 1
+INDEX_MAX_NETWORKS = 16
+INDEX_KEY_DTYPE = np.dtype([("index", "<u4"), ("space", "<u4")])
+INDEX_ENTRY_DTYPE = np.dtype([("index", "<u4"), ("space", "<u4"), ("key_id", "<u4"), ("flags", "<u4"),
+                              ("tunnel", "<u4"), ("remote_index", "<u4")])
+assert INDEX_ENTRY_DTYPE.itemsize == 24
+CIDR_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("bits", "u1"), ("reserved", "u1", (2,))])
+RX_SOURCE_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("reserved", "u1", (3,))])
+assert CIDR_DTYPE.itemsize == 20 and RX_SOURCE_DTYPE.itemsize == 20
 
 # neb_plain_packet (include/nebula_aead.h): one MultiCoalescer.Commit
 PLAIN_PARSED, PLAIN_FRAG_ANY, PLAIN_SKIP = 1, 2, 4
@@ -149,6 +159,14 @@ SIGNATURES = {
     "neb_rx_coalesce_batch_host": (_i, [_vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32]),
     "neb_rx_plain_from_wire": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "neb_rx_plain_from_wire_host": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
+    "neb_index_table_create": (_i, [_vp, _u32, C.POINTER(_vp)]),
+    "neb_index_table_destroy": (_i, [_vp]),
+    "neb_index_table_update": (_i, [_vp, _vp, _u32, _vp, _u32, _vp]),
+    "neb_index_table_set_own_networks": (_i, [_vp, _vp, _u32, _vp]),
+    "neb_index_table_count": (_i, [_vp, C.POINTER(_u32)]),
+    "neb_index_table_probe": (_i, [_vp, _u32, _u32, C.POINTER(_u32)]),
+    "neb_rx_resolve_batch": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "neb_rx_resolve_batch_host": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
     "neb_seal_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_open_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_seal_batch_sharded": (_i, [_i, _vp, _u32, _u32]),

@@ -1,0 +1,139 @@
+"""The hostmap's receive-side index lookups as a table (neb_index_table_*, neb_rx_resolve_batch[_host],
+include/nebula_aead.h): what readOutsidePackets looks up per datagram before it decrypts — the
+tunnel of the header's remote index (outside.go:93-106, hostmap.go:546-577), the double-encryption
+check on the UDP source (outside.go:66-74) and a relay's type and target (outside.go:201-240) — for
+a whole receive batch in one call, in front of rx_open_wire_batch, relay_forward_batch and
+rx_open_via_batch."""
+from __future__ import annotations
+
+import ctypes as C
+import ipaddress
+from typing import Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib as L
+
+
+def _vp(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def entries(rows: Iterable[Tuple[int, int, int, int, int, int]]) -> np.ndarray:
+    """[(space, index, key_id, flags, route tunnel, route remote_index)] -> INDEX_ENTRY_DTYPE"""
+    rows = list(rows)
+    out = np.zeros(len(rows), L.INDEX_ENTRY_DTYPE)
+    for k, (space, index, key_id, flags, tunnel, remote_index) in enumerate(rows):
+        out[k] = (index, space, key_id, flags, tunnel, remote_index)
+    return out
+
+
+def sources(addrs: Sequence[Optional[str]]) -> np.ndarray:
+    """UDP source addresses (None: unknown, family 0) -> RX_SOURCE_DTYPE. "::ffff:a.b.c.d" stays a
+    16-byte address, as an unmapped listener never hands it over (udp/udp_linux.go:245)."""
+    out = np.zeros(len(addrs), L.RX_SOURCE_DTYPE)
+    for k, a in enumerate(addrs):
+        if a is None:
+            continue
+        ip = ipaddress.ip_address(a)
+        out[k]["family"] = ip.version
+        out[k]["addr"][:len(ip.packed)] = np.frombuffer(ip.packed, np.uint8)
+    return out
+
+
+class IndexTable:
+    """One neb_index_table. engine=None: host-only (resolve_host only)."""
+
+    def __init__(self, engine, capacity: int):
+        self.engine = engine
+        self.capacity = capacity
+        self.handle = C.c_void_p()
+        L.check(L.lib().neb_index_table_create(engine.handle if engine is not None else None, capacity,
+                                               C.byref(self.handle)), "neb_index_table_create")
+
+    def close(self) -> None:
+        if self.handle:
+            L.lib().neb_index_table_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def update(self, delete: Sequence[Tuple[int, int]] = (), put=(), stream=None) -> None:
+        """delete: [(space, index)], applied first; put: INDEX_ENTRY_DTYPE or rows for entries().
+        With an engine the device image follows on `stream` (torch's current one by default)."""
+        dl = np.zeros(len(delete), L.INDEX_KEY_DTYPE)
+        for k, (space, index) in enumerate(delete):
+            dl[k] = (index, space)
+        pt = put if isinstance(put, np.ndarray) else entries(put)
+        pt = np.ascontiguousarray(pt, dtype=L.INDEX_ENTRY_DTYPE)
+        L.check(L.lib().neb_index_table_update(self.handle, _vp(dl), len(dl), _vp(pt), len(pt),
+                                               C.c_void_p(self._stream(stream))), "neb_index_table_update")
+
+    def set_own_networks(self, networks: Sequence[str]) -> None:
+        """networks: prefixes such as "10.1.0.0/16" or "fd00::/64" (the node's own VPN networks)."""
+        nets = np.zeros(len(networks), L.CIDR_DTYPE)
+        for k, s in enumerate(networks):
+            n = ipaddress.ip_network(s, strict=False)
+            nets[k]["family"], nets[k]["bits"] = n.version, n.prefixlen
+            b = n.network_address.packed
+            nets[k]["addr"][:len(b)] = np.frombuffer(b, np.uint8)
+        L.check(L.lib().neb_index_table_set_own_networks(self.handle, _vp(nets), len(nets), None),
+                "neb_index_table_set_own_networks")
+
+    def count(self) -> int:
+        live = C.c_uint32()
+        L.check(L.lib().neb_index_table_count(self.handle, C.byref(live)), "neb_index_table_count")
+        return live.value
+
+    def probe(self, space: int, index: int) -> Tuple[bool, int, int]:
+        """(found, slot, probes) from the host copy."""
+        out = (C.c_uint32 * 3)()
+        L.check(L.lib().neb_index_table_probe(self.handle, space, index, out), "neb_index_table_probe")
+        return bool(out[0]), out[1], out[2]
+
+    def resolve_host(self, packets: np.ndarray, arena: np.ndarray, src: Optional[np.ndarray] = None,
+                     want_route: bool = True, want_via: bool = True):
+        """neb_rx_resolve_batch_host. packets: RX_PACKET_DTYPE, contiguous; key_id and the
+        RX_OWN_SOURCE bit of len are written in place. Returns (route or None, via or None)."""
+        if packets.dtype != L.RX_PACKET_DTYPE or not packets.flags.c_contiguous:
+            raise ValueError("packets: a contiguous RX_PACKET_DTYPE array (updated in place)")
+        n = len(packets)
+        if src is not None and len(src) != n:
+            raise ValueError("one source per packet")
+        src = None if src is None else np.ascontiguousarray(src, dtype=L.RX_SOURCE_DTYPE)
+        route = np.zeros(n, L.RELAY_ROUTE_DTYPE) if want_route else None
+        via = np.zeros(n, L.RX_VIA_DTYPE) if want_via else None
+        rc = L.lib().neb_rx_resolve_batch_host(self.handle, _vp(packets), _vp(src), n, _vp(arena), arena.nbytes,
+                                               _vp(route), _vp(via))
+        L.check(rc, "neb_rx_resolve_batch_host")
+        return route, via
+
+    def resolve_device(self, d_packets, d_arena, d_src=None, d_route=None, d_via=None, stream=None) -> None:
+        """neb_rx_resolve_batch with everything in device memory (torch uint8 tensors of
+        RX_PACKET_DTYPE / RX_SOURCE_DTYPE / RELAY_ROUTE_DTYPE / RX_VIA_DTYPE records). Only enqueues:
+        the outputs are valid for later work on the same stream."""
+        n = d_packets.numel() // L.RX_PACKET_DTYPE.itemsize
+        for t, dt in ((d_src, L.RX_SOURCE_DTYPE), (d_route, L.RELAY_ROUTE_DTYPE), (d_via, L.RX_VIA_DTYPE)):
+            if t is not None and t.numel() // dt.itemsize != n:
+                raise ValueError("one record per packet")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        rc = L.lib().neb_rx_resolve_batch(self.engine.handle if self.engine is not None else None, self.handle,
+                                          p(d_packets), p(d_src), n, p(d_arena), p(d_route), p(d_via),
+                                          C.c_void_p(self._stream(stream)))
+        L.check(rc, "neb_rx_resolve_batch")
+
+    def _stream(self, stream):
+        if stream is not None:
+            return stream
+        if self.engine is None:
+            return None
+        import torch
+
+        return torch.cuda.current_stream().cuda_stream
+
+
+__all__ = ["IndexTable", "entries", "sources"]
