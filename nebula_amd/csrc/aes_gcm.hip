@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "../../include/nebula_aead.h"
+#include "cipher.hpp"
 #include "device_common.hpp"
 #include "knobs.hpp"
 #include "layout.hpp"
@@ -1408,7 +1409,7 @@ __global__ __launch_bounds__(kTailWaves * kWave) void gcm_single_tail_kernel(Gcm
 // payload (+ tag) into the kernel's argument block, which the runtime writes to device memory with
 // the dispatch, so the kernel reads nothing over PCIe; it writes the result and the status into
 // the caller's pinned staging (posted writes). One wave, 64 lanes per packet (2 rounds for 1300 B).
-constexpr uint32_t kOneBytes = 2048;  // AAD (padded to 16) + payload (+ tag): larger packets take the batch path
+// The block holds kOneBytes of packet (cipher.hpp).
 
 // The status goes out last, behind a system-scope release of the wave's result stores, so the host
 // may take the result as soon as it sees the status word change (engine.cpp one_packet) instead of
@@ -1506,11 +1507,9 @@ __global__ __launch_bounds__(kOneFillThreads) void gcm_one_kernel(OneArgs a) {
 // so the key record's loads do not wait for a PCIe round trip (17.5 µs per launch with the
 // descriptors in the pinned buffer, round-6 trace).
 constexpr int kOneBatchWaves = 4;
-constexpr uint32_t kOneBatchMax = 32;  // engine.cpp kCombMax
 struct OneBatchDescs {
-    neb_desc d[kOneBatchMax];
+    neb_desc d[kCombMax];
 };
-constexpr uint32_t kCombSlot = kOneBytes + 64u;  // AAD | payload (+ tag), room for the tag a seal appends
 struct OneBatchLds {
     uint2 ttab[256 * 32];  // 64 KiB T-table pairs, 32 copies
     struct KeyTabs {
@@ -2230,7 +2229,7 @@ extern "C" hipError_t neb_copy_desc(neb_desc* dst, const neb_desc* src, uint32_t
 
 extern "C" hipError_t neb_gcm_one_batch(int open, const neb_desc* descs, int32_t* status, uint8_t* slots, uint32_t n,
                                         const uint32_t* d_keys, uint32_t max_keys, hipStream_t s) {
-    if (n == 0 || n > neb::kOneBatchMax) return hipErrorInvalidValue;
+    if (n == 0 || n > neb::kCombMax) return hipErrorInvalidValue;
     neb::OneBatchDescs a;
     std::memcpy(a.d, descs, n * sizeof(neb_desc));
     const dim3 grid((n + neb::kOneBatchWaves - 1) / neb::kOneBatchWaves), block(neb::kOneBatchWaves * neb::kWave);

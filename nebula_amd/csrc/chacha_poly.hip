@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "../../include/nebula_aead.h"
+#include "cipher.hpp"
 #include "device_common.hpp"
 #include "layout.hpp"
 #include "rxwin.hpp"
@@ -404,6 +405,7 @@ __global__ __launch_bounds__(kChThreads) void chacha_batch_kernel(ChachaArgs arg
 
 // One packet, its bytes in the kernel arguments (the per-packet path; aes_gcm.hip gcm_one_kernel
 // has the why): lanes 0-15 of one wave.
+// Its own limit: the engine does not rely on it equalling kOneBytes (neb_chacha_one refuses what does not fit).
 constexpr uint32_t kChOneBytes = 2048;
 struct ChOneArgs {
     neb_desc d;  // offsets from `in`; dst_off = the output's address (rebased in the kernel)

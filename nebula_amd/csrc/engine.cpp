@@ -36,40 +36,8 @@
 #include "timing.hpp"
 #include "tx.hpp"
 #include "coalesce.hpp"
+#include "cipher.hpp"
 #include "engine_internal.hpp"
-
-// n keys (32 B each, mapped host memory) into the records of key slots slots[0..n): one launch
-extern "C" hipError_t neb_gcm_key_setup(const uint8_t* keys, const uint32_t* slots, uint32_t n, uint32_t* table,
-                                        hipStream_t s);
-extern "C" hipError_t neb_chacha_key_setup(const uint8_t* keys, const uint32_t* slots, uint32_t n, uint32_t* table,
-                                           hipStream_t s);
-extern "C" hipError_t neb_fence_keys(const neb_desc* in, neb_desc* out, uint32_t n, const uint8_t* bad,
-                                     uint32_t nbad, hipStream_t s);
-extern "C" hipError_t neb_gcm_batch_single(int open, const neb_desc* d_desc, uint32_t n, uint8_t* d_arena,
-                                           const uint32_t* d_keys, uint32_t max_keys, uint32_t key_hint,
-                                           int32_t* d_status, const uint32_t* d_n, int cu_count, hipStream_t s,
-                                           int hdr_from_dst, hipEvent_t stop, const uint8_t* rx);
-extern "C" hipError_t neb_gcm_one(int open, const uint8_t* aad, uint32_t aad_len, const uint8_t* in, uint32_t in_len,
-                                  uint32_t len, uint64_t counter, uint8_t* out, int32_t* status, const uint32_t* d_keys,
-                                  uint32_t max_keys, uint32_t key, hipStream_t s);
-extern "C" hipError_t neb_copy_desc(neb_desc* dst, const neb_desc* src, uint32_t n, hipStream_t s);
-extern "C" hipError_t neb_gcm_one_batch(int open, const neb_desc* descs, int32_t* status, uint8_t* slots, uint32_t n,
-                                        const uint32_t* d_keys, uint32_t max_keys, hipStream_t s);
-extern "C" hipError_t neb_chacha_one(int open, const uint8_t* aad, uint32_t aad_len, const uint8_t* in,
-                                     uint32_t in_len, uint32_t len, uint64_t counter, uint8_t* out, int32_t* status,
-                                     const uint32_t* d_keys, uint32_t max_keys, uint32_t key, hipStream_t s);
-extern "C" hipError_t neb_gcm_batch_chunked(int open, const neb_desc* d_desc, uint32_t n, uint8_t* d_arena,
-                                            const uint32_t* d_keys, uint32_t max_keys, int32_t* d_status,
-                                            const uint32_t* d_sorted, const uint4* d_chunks,
-                                            uint32_t* d_counters, uint32_t max_chunks,
-                                            int cu_count, hipStream_t s, int hdr_from_dst, hipEvent_t stop,
-                                            const uint8_t* rx);
-extern "C" hipError_t neb_gcm_probe(void);
-extern "C" uint32_t neb_gcm_single_slots(uint32_t n, int cu_count, int open, int hdr_from_dst);
-extern "C" hipError_t neb_chacha_batch(int open, const neb_desc* d_desc, uint32_t n, uint8_t* d_arena,
-                                       const uint32_t* d_keys, uint32_t max_keys, uint32_t key_hint,
-                                       int32_t* d_status, const uint32_t* d_n, int cu_count, hipStream_t s,
-                                       int hdr_from_dst, hipEvent_t stop, const uint8_t* rx);
 
 // Device workspace of the mixed-key scheduler (sched.hpp). One per engine (and per queue batch,
 // receive slot and window set); batches on different streams never overlap in it (workspace.hpp).
@@ -84,28 +52,31 @@ struct SchedSpace {
 namespace {
 
 constexpr size_t kStageMin = 1 << 16;
+using neb::DevBuf;
+using neb::PinnedBuf;
+using neb::kCombMax;  // cipher.hpp
+using neb::kCombSlot;
 using neb::kPipeChunkPkts;  // pipe_core.hpp: the staged host pipeline's chunk plan and spans
 using neb::kPipeSlots;
 
 struct PipeSlot {
-    uint8_t* d_buf = nullptr;
-    size_t d_cap = 0;
-    neb_desc* h_desc = nullptr;  // pinned: the chunk's rebased descriptors
-    neb_desc* d_desc = nullptr;  // their device copy, which the kernels read
-    int32_t* h_status = nullptr; // pinned, mapped: the kernels write it in place
+    DevBuf<> d_buf;
+    PinnedBuf<neb_desc> h_desc;   // the chunk's rebased descriptors
+    DevBuf<neb_desc> d_desc;      // their device copy, which the kernels read
+    PinnedBuf<int32_t> h_status;  // mapped: the kernels write it in place
     int32_t* user_status = nullptr;
     uint32_t user_begin = 0, count = 0;
     neb::PipeSpan span;             // arena span of the chunk in flight (count > 0)
-    hipEvent_t in_done = nullptr;   // the chunk's copies in are done (the kernel waits for it)
-    hipEvent_t k_done = nullptr;    // its kernel is done (the copies back wait for it)
-    hipEvent_t done = nullptr;      // its span and statuses are back (the slot is free)
+    neb::Event in_done;  // the chunk's copies in are done (the kernel waits for it)
+    neb::Event k_done;   // its kernel is done (the copies back wait for it)
+    neb::Event done;     // its span and statuses are back (the slot is free)
 };
 struct Pipe {
-    hipStream_t h2d = nullptr, comp = nullptr, d2h = nullptr;
+    neb::Stream h2d, comp, d2h;
     PipeSlot slot[kPipeSlots];
-    SchedSpace* sched = nullptr;  // the compute stream's mixed-key workspace
+    SchedSpace sched;  // the compute stream's mixed-key workspace
 
-    int ensure(neb_engine* e);         // streams, events and slot buffers, created once
+    int ensure(neb_engine* e);         // streams, events and slot buffers: whatever is missing
     hipError_t retire(PipeSlot& s);    // wait for the slot's chunk, hand its statuses to the caller
     void drain();                      // after a failure: nothing queued, no chunk in flight
 };
@@ -129,8 +100,8 @@ struct TxSpace {
     uint32_t n_cap = 0, tun_cap = 0, wire_cap = 0;
     neb::TxWs ws{};
     // through a relay (neb_tx_seal_via_batch): the relay tunnels' one key, read back for the outer seal
-    uint32_t* h_via_key = nullptr;  // pinned
-    hipEvent_t via_ev = nullptr;
+    PinnedBuf<uint32_t> h_via_key;
+    neb::Event via_ev;
     std::mutex mu;
 };
 
@@ -153,9 +124,8 @@ struct CoSpace {
 // over more than 8 engines leaked one per call, and at 64 threads p99 was 100x p50.)
 constexpr uint32_t kPktSlots = 4;
 struct PktSlot {
-    hipStream_t stream = nullptr;
-    uint8_t* h = nullptr;
-    size_t cap = 0;
+    neb::Stream stream;
+    PinnedBuf<> h;
 };
 struct PktWaiter {
     std::condition_variable cv;
@@ -175,13 +145,12 @@ struct PktPool {
 // every status, wakes the others, and each copies its own result out. A call that finds a launch
 // free launches alone as before (the packet in the kernel arguments), so up to kPktSlots threads see
 // no change; past that the batches grow with the offered load.
-constexpr uint32_t kCombMax = 32;
-constexpr uint32_t kCombSlot = 2048u + 64u;  // aes_gcm.hip kCombSlot: AAD | payload (+ tag) of one request
-constexpr size_t kCombDescOff = 0, kCombStatusOff = 2048, kCombSlotsOff = 4096;
+constexpr size_t kCombDescOff = 0, kCombStatusOff = 2u << 10, kCombSlotsOff = 4u << 10;  // 2 KiB for each
+static_assert(kCombMax * sizeof(neb_desc) <= kCombStatusOff && kCombMax * 4u <= kCombSlotsOff - kCombStatusOff, "");
 constexpr size_t kCombBytes = kCombSlotsOff + (size_t)kCombMax * kCombSlot;
 struct CombBatch {
-    uint8_t* h = nullptr;  // pinned, mapped: descriptors | statuses | slots
-    uint32_t n = 0;        // requests joined
+    PinnedBuf<> h;   // mapped: descriptors | statuses | slots
+    uint32_t n = 0;  // requests joined
     int alg = 0, open = 0;
     bool launched = false;  // (PktComb::mu)
     hipStream_t stream = nullptr;
@@ -211,21 +180,22 @@ struct PktComb {
     uint32_t solo = 0;              // of them alone (each holds a pool slot), at most kPktSlots
     std::condition_variable launch_cv;  // a launch completed (the leaders of gathering batches wait)
     CombBatch* open[2][2] = {};     // accepting requests: [AES-GCM / ChaCha20][seal / open]
-    std::vector<CombBatch*> free_, all;
+    std::vector<CombBatch*> free_;
+    std::vector<std::unique_ptr<CombBatch>> all;
     uint32_t next = 0;              // the per-packet pool's streams carry the combined launches in turn
     std::atomic<uint64_t> launches{0}, combined{0};
 };
 struct KeyUse {
     hipStream_t s;
-    hipEvent_t ev;
+    neb::Event ev;
 };
 
 struct neb_engine {
     int device = 0;
     int cu_count = 0;
-    hipStream_t stream = nullptr;
+    neb::Stream stream;
     uint32_t max_keys = 0;
-    uint32_t* d_keys = nullptr;
+    DevBuf<uint32_t> d_keys;
     std::vector<int> slot_alg;  // 0 = free, -1 = reserved by an install in progress
     // Install id of the key in each slot (0 = none): unique per neb_cipher_create /
     // neb_cipher_create_batch key, shared by the engines of one neb_cipher_create_multi. Batches
@@ -249,9 +219,8 @@ struct neb_engine {
     std::mutex pipe_mu;
     Pipe pipe;
     // zero-copy host batches: device copies of pageable descriptors / statuses
-    neb_desc* zc_desc = nullptr;
-    int32_t* zc_status = nullptr;
-    uint32_t zc_cap = 0;
+    DevBuf<neb_desc> zc_desc;
+    DevBuf<int32_t> zc_status;
 
     SchedSpace sched;
     TxSpace tx;
@@ -261,17 +230,16 @@ struct neb_engine {
     // workspace) of its own, so consecutive chunks overlap on the device; descriptors and statuses
     // staged in pinned memory; one event per chunk.
     struct RxSlot {
-        hipStream_t stream = nullptr;
-        hipEvent_t ev = nullptr;
-        SchedSpace* sched = nullptr;
+        neb::Stream stream;
+        neb::Event ev;
+        SchedSpacePtr sched;
     };
     struct RxSpace {
         std::mutex mu;  // held from neb_rx_pipe_begin to neb_rx_pipe_end
-        neb_desc* h_desc = nullptr;
-        int32_t* h_status = nullptr;
-        neb_desc* d_desc = nullptr;
-        int32_t* d_status = nullptr;
-        uint32_t cap = 0;
+        PinnedBuf<neb_desc> h_desc;
+        PinnedBuf<int32_t> h_status;
+        DevBuf<neb_desc> d_desc;
+        DevBuf<int32_t> d_status;
         std::vector<RxSlot> slot;
     } rx;
 
@@ -360,26 +328,10 @@ class PktLease {
     // its kernel has published the status word, so the previous lease's kernel may still be draining
     // on the slot's stream: wait for it before the buffer it writes is freed.
     bool reserve(size_t bytes) {
-        if (bytes <= s_->cap) return true;
-        if (s_->h) {
-            const hipError_t err = hipStreamSynchronize(s_->stream);
-            if (err != hipSuccess) {
-                set_error("PktLease::reserve", err);
-                return false;
-            }
-            hipHostFree(s_->h);
-        }
-        s_->h = nullptr;
-        s_->cap = 0;
-        const size_t cap = std::max(kStageMin, align_up(bytes, 1 << 16));
-        hipError_t err = hipHostMalloc((void**)&s_->h, cap, hipHostMallocDefault);
-        if (err != hipSuccess) {
-            set_error("hipHostMalloc", err);
-            s_->h = nullptr;
-            return false;
-        }
-        s_->cap = cap;
-        return true;
+        const hipError_t err = s_->h.reserve(std::max(kStageMin, align_up(bytes, 1 << 16)), nullptr,
+                                             [&] { return hipStreamSynchronize(s_->stream); });
+        if (err != hipSuccess) set_error("PktLease::reserve", err);
+        return err == hipSuccess;
     }
 
   private:
@@ -387,34 +339,28 @@ class PktLease {
     PktSlot* s_ = nullptr;
 };
 
-// After an asynchronous batch is enqueued on stream s: remember it for neb_cipher_destroy (the
-// key_hint's slot, or every slot for a mixed-key batch). Events skip the system-scope cache
-// flush (timing-only markers would carry it for nothing).
-static void note_use(neb_engine* e, uint32_t key_hint, hipStream_t s) {
-    std::lock_guard<std::mutex> g(e->use_mu);
-    std::vector<KeyUse>& v = key_hint == NEB_KEYS_MIXED ? e->mixed_use : e->key_use[key_hint];
-    for (KeyUse& u : v)
-        if (u.s == s) {
-            (void)hipEventRecord(u.ev, s);
-            return;
-        }
-    KeyUse u{s, nullptr};
-    if (hipEventCreateWithFlags(&u.ev, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) return;
-    (void)hipEventRecord(u.ev, s);
-    v.push_back(u);
-}
-
-// The key-use event of (key_hint, s), created on first use, for a batch to bind to its last
-// kernel (neb_gcm_batch_single's `stop`) instead of note_use's marker after it.
-static hipEvent_t use_event(neb_engine* e, uint32_t key_hint, hipStream_t s) {
-    std::lock_guard<std::mutex> g(e->use_mu);
+// The key-use event of (key_hint, s), created on first use (null when that fails); e->use_mu held.
+// Events skip the system-scope cache flush (timing-only markers would carry it for nothing).
+static hipEvent_t use_event_locked(neb_engine* e, uint32_t key_hint, hipStream_t s) {
     std::vector<KeyUse>& v = key_hint == NEB_KEYS_MIXED ? e->mixed_use : e->key_use[key_hint];
     for (KeyUse& u : v)
         if (u.s == s) return u.ev;
-    KeyUse u{s, nullptr};
-    if (hipEventCreateWithFlags(&u.ev, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) return nullptr;
-    v.push_back(u);
-    return u.ev;
+    KeyUse u{s, {}};
+    if (u.ev.create(hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) return nullptr;
+    v.push_back(std::move(u));
+    return v.back().ev;
+}
+// After an asynchronous batch is enqueued on stream s: remember it for neb_cipher_destroy (the
+// key_hint's slot, or every slot for a mixed-key batch).
+static void note_use(neb_engine* e, uint32_t key_hint, hipStream_t s) {
+    std::lock_guard<std::mutex> g(e->use_mu);
+    if (hipEvent_t ev = use_event_locked(e, key_hint, s)) (void)hipEventRecord(ev, s);
+}
+// The event for a batch to bind to its last kernel (neb_gcm_batch_single's `stop`) instead of
+// note_use's marker after it.
+static hipEvent_t use_event(neb_engine* e, uint32_t key_hint, hipStream_t s) {
+    std::lock_guard<std::mutex> g(e->use_mu);
+    return use_event_locked(e, key_hint, s);
 }
 
 extern "C" {
@@ -501,8 +447,8 @@ NEB_API int neb_engine_create(int device, uint32_t max_keys, neb_engine** out) {
     e->slot_alg.assign(max_keys, 0);
     e->slot_tag.assign(max_keys, 0);
     e->key_use.resize(max_keys);
-    bool ok = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc((void**)&e->d_keys, (size_t)max_keys * neb::kKeyRecBytes) == hipSuccess &&
+    bool ok = e->stream.create(hipStreamNonBlocking) == hipSuccess &&
+              e->d_keys.reserve((size_t)max_keys * neb::kKeyRecBytes) == hipSuccess &&
               hipMemset(e->d_keys, 0, (size_t)max_keys * neb::kKeyRecBytes) == hipSuccess &&
               hipStreamSynchronize(nullptr) == hipSuccess;  // the null-stream memset, before any stream reads keys
     // The per-packet pool's streams: high priority, which HIP gives a hardware queue of its own each.
@@ -513,12 +459,9 @@ NEB_API int neb_engine_create(int device, uint32_t max_keys, neb_engine** out) {
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
     for (PktSlot& sl : e->pkt.slot) {
-        ok = ok && hipStreamCreateWithPriority(&sl.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
-             hipHostMalloc((void**)&sl.h, kStageMin, hipHostMallocDefault) == hipSuccess;
-        if (ok) {
-            sl.cap = kStageMin;
-            e->pkt.free_[e->pkt.nfree++] = &sl;
-        }
+        ok = ok && sl.stream.create_priority(hipStreamNonBlocking, greatest) == hipSuccess &&
+             sl.h.reserve(kStageMin) == hipSuccess;
+        if (ok) e->pkt.free_[e->pkt.nfree++] = &sl;
     }
     if (!ok) {
         set_error("engine allocation", hipGetLastError());
@@ -529,51 +472,16 @@ NEB_API int neb_engine_create(int device, uint32_t max_keys, neb_engine** out) {
     return NEB_OK;
 }
 
+// Every stream the engine made is waited for, then the members release themselves (hip_owned.hpp;
+// each workspace waits for its last batch), here, with the engine's device current.
 NEB_API int neb_engine_destroy(neb_engine* e) {
     if (!e) return NEB_ERR_INVALID;
     DeviceGuard dg(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
-    for (hipStream_t st : {e->pipe.h2d, e->pipe.comp, e->pipe.d2h})
-        if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
-    for (CombBatch* b : e->comb.all) {
-        if (b->h) hipHostFree(b->h);
-        delete b;
-    }
-    for (auto& s : e->pipe.slot) {
-        for (hipEvent_t ev : {s.in_done, s.k_done, s.done})
-            if (ev) hipEventDestroy(ev);
-        if (s.d_buf) hipFree(s.d_buf);
-        if (s.h_desc) hipHostFree(s.h_desc);
-        if (s.d_desc) hipFree(s.d_desc);
-        if (s.h_status) hipHostFree(s.h_status);
-    }
-    // the workspaces (each waits for its last batch) here, with the device current, not in ~neb_engine
-    neb_sched_space_free(e->pipe.sched);
-    e->sched.dev.destroy();
-    e->tx.dev.destroy();
-    if (e->tx.h_via_key) hipHostFree(e->tx.h_via_key);
-    if (e->tx.via_ev) hipEventDestroy(e->tx.via_ev);
-    e->co.dev.destroy();
-    for (auto& r : e->rx.slot) {
-        if (r.stream) { hipStreamSynchronize(r.stream); hipStreamDestroy(r.stream); }
-        if (r.ev) hipEventDestroy(r.ev);
-        neb_sched_space_free(r.sched);
-    }
-    if (e->rx.h_desc) hipHostFree(e->rx.h_desc);
-    if (e->rx.h_status) hipHostFree(e->rx.h_status);
-    if (e->rx.d_desc) hipFree(e->rx.d_desc);
-    if (e->rx.d_status) hipFree(e->rx.d_status);
-    if (e->zc_desc) hipFree(e->zc_desc);
-    if (e->zc_status) hipFree(e->zc_status);
-    if (e->d_keys) hipFree(e->d_keys);
-    for (PktSlot& sl : e->pkt.slot) {
-        if (sl.stream) { hipStreamSynchronize(sl.stream); hipStreamDestroy(sl.stream); }
-        if (sl.h) hipHostFree(sl.h);
-    }
-    for (auto& v : e->key_use)
-        for (KeyUse& u : v) hipEventDestroy(u.ev);
-    for (KeyUse& u : e->mixed_use) hipEventDestroy(u.ev);
-    if (e->stream) hipStreamDestroy(e->stream);
+    e->pipe.drain();
+    for (auto& r : e->rx.slot) hipStreamSynchronize(r.stream);  // (a slot in the list is complete)
+    for (PktSlot& sl : e->pkt.slot)
+        if (sl.stream) hipStreamSynchronize(sl.stream);
     delete e;
     return NEB_OK;
 }
@@ -798,7 +706,6 @@ NEB_API int neb_cipher_destroy(neb_cipher* c) {
     }
     {
         std::lock_guard<std::mutex> g(e->use_mu);
-        for (KeyUse& u : e->key_use[slot]) hipEventDestroy(u.ev);
         e->key_use[slot].clear();
     }
     {
@@ -1033,7 +940,7 @@ static int one_packet(neb_cipher* c, int open, const uint8_t* ad, size_t ad_len,
                       size_t pay_len, uint64_t n, uint8_t* dst, int32_t* st_out) {
     neb_engine* e = c->e;
     const size_t pay = align_up(ad_len, 16);
-    if (c->alg != NEB_ALG_AESGCM || pay + std::max(in_len, pay_len + 16) > kCombSlot || pay + in_len > 2048)
+    if (c->alg != NEB_ALG_AESGCM || pay + std::max(in_len, pay_len + 16) > kCombSlot || pay + in_len > neb::kOneBytes)
         return one_packet_solo(c, open, ad, ad_len, in, in_len, pay_len, n, dst, st_out);
     static const uint32_t max_inflight = [] {  // NEB_PKT_INFLIGHT: launches in flight (A/B), default 4
         const char* v = std::getenv("NEB_PKT_INFLIGHT");
@@ -1060,15 +967,14 @@ static int one_packet(neb_cipher* c, int open, const uint8_t* ad, size_t ad_len,
     DeviceGuard dg(e->device);
     if (!ob) {
         if (cb.free_.empty()) {
-            auto* nb = new (std::nothrow) CombBatch;
+            std::unique_ptr<CombBatch> nb(new (std::nothrow) CombBatch);
             if (!nb) return NEB_ERR_INVALID;
-            if (hipHostMalloc((void**)&nb->h, kCombBytes, hipHostMallocDefault) != hipSuccess) {
-                delete nb;
-                set_error("hipHostMalloc (per-packet batch)", hipErrorOutOfMemory);
+            if (nb->h.reserve(kCombBytes) != hipSuccess) {
+                set_error("pinned memory (per-packet batch)", hipErrorOutOfMemory);
                 return NEB_ERR_HIP;
             }
-            cb.all.push_back(nb);
-            cb.free_.push_back(nb);
+            cb.free_.push_back(nb.get());
+            cb.all.push_back(std::move(nb));
         }
         ob = cb.free_.back();
         cb.free_.pop_back();
@@ -1334,14 +1240,10 @@ bool neb_host_mapped(const void* p) { return host_mapped(p); }  // queue.cpp
 static int batch_host_zero_copy(neb_engine* e, int alg, int open, const neb_desc* desc, uint32_t n,
                                 uint8_t* arena, size_t arena_len, int32_t* status, uint32_t key_hint) {
     const bool desc_mapped = host_mapped(desc), status_mapped = host_mapped(status);
-    if ((!desc_mapped || !status_mapped) && n > e->zc_cap) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (e->zc_desc) { hipFree(e->zc_desc); e->zc_desc = nullptr; }
-        if (e->zc_status) { hipFree(e->zc_status); e->zc_status = nullptr; }
-        e->zc_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->zc_desc, (size_t)n * sizeof(neb_desc)));
-        HIP_TRY(hipMalloc((void**)&e->zc_status, (size_t)n * sizeof(int32_t)));
-        e->zc_cap = n;
+    if (!desc_mapped || !status_mapped) {
+        auto idle = [&] { return hipStreamSynchronize(e->stream); };
+        HIP_TRY(e->zc_desc.reserve((size_t)n * sizeof(neb_desc), nullptr, idle));
+        HIP_TRY(e->zc_status.reserve((size_t)n * sizeof(int32_t), nullptr, idle));
     }
     const neb_desc* d_desc = desc;
     int32_t* d_status = status;
@@ -1364,21 +1266,17 @@ static int batch_host_zero_copy(neb_engine* e, int alg, int open, const neb_desc
 // of the pipeline's could land on one, so a chunk's kernel queued behind the previous chunk's copy
 // back. Such streams are blocking streams: they and the null stream wait on each other.
 int Pipe::ensure(neb_engine* e) {
-    for (hipStream_t* st : {&h2d, &comp, &d2h}) {
-        if (*st) continue;
+    if (!h2d || !comp || !d2h) {
         std::vector<uint32_t> mask(((uint32_t)e->cu_count + 31u) / 32u, 0u);
         for (int c = 0; c < e->cu_count; c++) mask[c / 32] |= 1u << (c % 32);
-        HIP_TRY(hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()));
+        for (neb::Stream* st : {&h2d, &comp, &d2h}) HIP_TRY(st->create_cu_mask((uint32_t)mask.size(), mask.data()));
     }
-    if (!sched && !(sched = new (std::nothrow) SchedSpace)) return NEB_ERR_INVALID;
+    // each create and reserve does nothing for what exists: a slot that a failure left half built is completed
     for (auto& s : slot) {
-        if (!s.done) {
-            for (hipEvent_t* ev : {&s.in_done, &s.k_done, &s.done})
-                HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-            HIP_TRY(hipHostMalloc((void**)&s.h_desc, kPipeChunkPkts * sizeof(neb_desc), hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void**)&s.d_desc, kPipeChunkPkts * sizeof(neb_desc)));
-            HIP_TRY(hipHostMalloc((void**)&s.h_status, kPipeChunkPkts * sizeof(int32_t), hipHostMallocDefault));
-        }
+        for (neb::Event* ev : {&s.in_done, &s.k_done, &s.done}) HIP_TRY(ev->create(hipEventDisableTiming));
+        HIP_TRY(s.h_desc.reserve(kPipeChunkPkts * sizeof(neb_desc)));
+        HIP_TRY(s.d_desc.reserve(kPipeChunkPkts * sizeof(neb_desc)));
+        HIP_TRY(s.h_status.reserve(kPipeChunkPkts * sizeof(int32_t)));
         s.count = 0;
     }
     return NEB_OK;
@@ -1399,7 +1297,8 @@ hipError_t Pipe::retire(PipeSlot& s) {
 }
 
 void Pipe::drain() {
-    for (hipStream_t st : {h2d, comp, d2h}) (void)hipStreamSynchronize(st);
+    for (const neb::Stream* st : {&h2d, &comp, &d2h})
+        if (*st) (void)hipStreamSynchronize(*st);
     for (auto& s : slot) s.count = 0;
 }
 
@@ -1463,12 +1362,7 @@ static int batch_host(neb_engine* e, int alg, int open, const neb_desc* desc, ui
         for (auto& o : P.slot)
             if (&o != &s && o.count && o.span.overlaps(sp)) PIPE_TRY(P.retire(o));
         const size_t bytes = (size_t)(sp.hi - sp.lo);
-        if (bytes > s.d_cap) {  // (retired: nothing in flight uses it)
-            if (s.d_buf) { hipFree(s.d_buf); s.d_buf = nullptr; s.d_cap = 0; }
-            const size_t cap = align_up(bytes, 1 << 20);
-            PIPE_TRY(hipMalloc((void**)&s.d_buf, cap));
-            s.d_cap = cap;
-        }
+        PIPE_TRY(s.d_buf.reserve(align_up(bytes, 1 << 20)));  // (retired: nothing in flight uses it)
         neb::pipe_rebase(s.h_desc, desc + begin, cnt, sp.lo);
         s.span = sp;
         s.user_status = status;
@@ -1483,7 +1377,7 @@ static int batch_host(neb_engine* e, int alg, int open, const neb_desc* desc, ui
         // copy-in stream the small copy's latency left that stream idle between chunks.
         PIPE_TRY(hipStreamWaitEvent(P.comp, s.in_done, 0));
         PIPE_TRY(neb_copy_desc(s.d_desc, s.h_desc, cnt, P.comp));
-        PIPE_TRY(launch_batch(e, alg, open, s.d_desc, cnt, s.d_buf, s.h_status, key_hint, P.comp, nullptr, P.sched));
+        PIPE_TRY(launch_batch(e, alg, open, s.d_desc, cnt, s.d_buf, s.h_status, key_hint, P.comp, nullptr, &P.sched));
         PIPE_TRY(hipEventRecord(s.k_done, P.comp));
         if (k == 0 && !check_upto(n)) {  // the rest of the batch, while chunk 0 is copied in and run
             P.drain();
@@ -1528,35 +1422,23 @@ bool neb_rx_pipe_begin(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena
     };
     while (r.slot.size() < nchunks) {
         neb_engine::RxSlot sl;
-        sl.sched = new (std::nothrow) SchedSpace;
+        sl.sched.reset(neb_sched_space_new());
         // the kernels' stores into the mapped arena must be visible to the host at the event
-        if (!sl.sched || hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) {
-            if (sl.stream) hipStreamDestroy(sl.stream);
-            delete sl.sched;
+        if (!sl.sched || sl.stream.create(hipStreamNonBlocking) != hipSuccess ||
+            sl.ev.create(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess)
             return fail();
-        }
-        r.slot.push_back(sl);
+        r.slot.push_back(std::move(sl));
     }
-    if (n > r.cap) {
-        for (auto& sl : r.slot)
-            if (hipStreamSynchronize(sl.stream) != hipSuccess) return fail();
-        if (r.h_desc) hipHostFree(r.h_desc);
-        if (r.h_status) hipHostFree(r.h_status);
-        if (r.d_desc) hipFree(r.d_desc);
-        if (r.d_status) hipFree(r.d_status);
-        r.h_desc = nullptr;
-        r.h_status = nullptr;
-        r.d_desc = nullptr;
-        r.d_status = nullptr;
-        r.cap = 0;
-        if (hipHostMalloc((void**)&r.h_desc, (size_t)n * sizeof(neb_desc), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&r.h_status, (size_t)n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
-            hipMalloc((void**)&r.d_desc, (size_t)n * sizeof(neb_desc)) != hipSuccess ||
-            hipMalloc((void**)&r.d_status, (size_t)n * sizeof(int32_t)) != hipSuccess)
-            return fail();
-        r.cap = n;
-    }
+    auto idle = [&] {  // before a staging buffer is freed: nothing queued on any slot's stream
+        hipError_t err = hipSuccess;
+        for (size_t k = 0; k < r.slot.size() && err == hipSuccess; k++) err = hipStreamSynchronize(r.slot[k].stream);
+        return err;
+    };
+    if (r.h_desc.reserve((size_t)n * sizeof(neb_desc), nullptr, idle) != hipSuccess ||
+        r.h_status.reserve((size_t)n * sizeof(int32_t), nullptr, idle) != hipSuccess ||
+        r.d_desc.reserve((size_t)n * sizeof(neb_desc), nullptr, idle) != hipSuccess ||
+        r.d_status.reserve((size_t)n * sizeof(int32_t), nullptr, idle) != hipSuccess)
+        return fail();
     *h_desc = r.h_desc;
     *h_status = r.h_status;
     return true;
@@ -1570,7 +1452,7 @@ int neb_rx_pipe_submit(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena
     HIP_TRY(hipMemcpyAsync(r.d_desc + c0, r.h_desc + c0, (size_t)cnt * sizeof(neb_desc), hipMemcpyHostToDevice,
                            sl.stream));
     HIP_TRY(launch_batch(e, alg, 1, r.d_desc + c0, cnt, arena, r.d_status + c0, key_hint, sl.stream, nullptr,
-                         sl.sched));
+                         sl.sched.get()));
     HIP_TRY(hipMemcpyAsync(r.h_status + c0, r.d_status + c0, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost,
                            sl.stream));
     HIP_TRY(hipEventRecord(sl.ev, sl.stream));
@@ -1618,8 +1500,8 @@ static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, c
     if (d_via) {
         // the relay tunnels' one key, for a single-key outer seal: asked for first, read back after
         // the inner seal is enqueued, so the host waits for this word only while the device works
-        if (!tx.h_via_key) HIP_TRY(hipHostMalloc((void**)&tx.h_via_key, sizeof(uint32_t), hipHostMallocDefault));
-        if (!tx.via_ev) HIP_TRY(hipEventCreateWithFlags(&tx.via_ev, hipEventDisableTiming));
+        HIP_TRY(tx.h_via_key.reserve(sizeof(uint32_t)));
+        HIP_TRY(tx.via_ev.create(hipEventDisableTiming));
         HIP_TRY(neb_tx_via_key(d_tun, ntun, d_via, tx.h_via_key, s));
         HIP_TRY(hipEventRecord(tx.via_ev, s));
     }
@@ -1970,8 +1852,8 @@ static int batch_sharded(int alg, int open, const neb_shard* sh, uint32_t m, uin
     std::vector<neb_engine*> es(m);
     for (uint32_t k = 0; k < m; k++) es[k] = sh[k].e;
     const KeyFence fence = key_fence(es.data(), m);
-    // device copies of a fenced shard's descriptors (KeyFence; batch_host_multi), freed at the end
-    std::vector<void*> temps;
+    // device copies of a fenced shard's descriptors (KeyFence; batch_host_multi), freed on return
+    std::vector<DevBuf<>> temps;
     int rc = NEB_OK;
     uint32_t launched = 0;
     for (; launched < m && rc == NEB_OK; launched++) {  // every shard queued first, then all waited for
@@ -1989,14 +1871,13 @@ static int batch_sharded(int alg, int open, const neb_shard* sh, uint32_t m, uin
                 }
             } else {
                 const std::vector<uint8_t>& bad = fence.bad[launched];
-                void* t = nullptr;
                 const size_t db = align_up((size_t)s.n * sizeof(neb_desc), 256);
-                if (!s.d_desc || hipMalloc(&t, db + bad.size()) != hipSuccess) {
+                if (!s.d_desc || temps.emplace_back().reserve(db + bad.size()) != hipSuccess) {
                     rc = s.d_desc ? NEB_ERR_HIP : NEB_ERR_INVALID;
                     continue;
                 }
-                temps.push_back(t);
-                uint8_t* d_bad = (uint8_t*)t + db;
+                uint8_t* t = temps.back();
+                uint8_t* d_bad = t + db;
                 if (hipMemcpyAsync(d_bad, bad.data(), bad.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
                     neb_fence_keys(s.d_desc, (neb_desc*)t, s.n, d_bad, (uint32_t)bad.size(), st) != hipSuccess ||
                     hipStreamSynchronize(st) != hipSuccess) {  // `bad` is pageable and local
@@ -2016,7 +1897,6 @@ static int batch_sharded(int alg, int open, const neb_shard* sh, uint32_t m, uin
             rc = NEB_ERR_HIP;
         }
     }
-    for (void* t : temps) hipFree(t);
     return rc;
 }
 

@@ -4,9 +4,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "../../include/nebula_aead.h"
 #include "sched.hpp"
-#include "workspace.hpp"
+#include "workspace.hpp"  // (and hip_owned.hpp)
 
 struct SchedSpace;  // the mixed-key scheduler's device workspace
 
@@ -35,3 +37,8 @@ int neb_rx_pipe_submit(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena
 int neb_rx_pipe_wait(neb_engine* e, uint32_t k);
 void neb_rx_pipe_end(neb_engine* e);
 }
+
+struct SchedSpaceFree {
+    void operator()(SchedSpace* sp) const { neb_sched_space_free(sp); }
+};
+using SchedSpacePtr = std::unique_ptr<SchedSpace, SchedSpaceFree>;  // (neb_sched_space_new())

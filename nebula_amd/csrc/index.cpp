@@ -17,9 +17,9 @@
 #include "index_core.hpp"
 
 #if defined(__HIPCC__)
+#include "engine_internal.hpp"
 #include "hip_guard.hpp"
 #include "resolve.hpp"
-extern "C" int neb_engine_device_of(const neb_engine* e);  // engine.cpp
 #endif
 
 using namespace neb;
@@ -32,7 +32,7 @@ constexpr uint32_t kIdxStageOps = 4096;  // ops per scatter launch (two pinned s
 
 struct IdxUse {  // the last work a stream has enqueued on an image
     hipStream_t s;
-    hipEvent_t ev;
+    neb::Event ev;
 };
 #endif
 
@@ -53,15 +53,15 @@ struct neb_index_table {
     int device = -1;  // -1: host-only
     // dmu: which image is active, and the events (taken inside mu by writers, alone by resolves)
     mutable std::mutex dmu;
-    IdxSlot* image[2] = {nullptr, nullptr};
+    DevBuf<IdxSlot> image[2];
     int active = 0;
     mutable std::vector<IdxUse> uses[2];
-    IdxOp* stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    PinnedBuf<IdxOp> stage[2];
+    Event stage_ev[2];
     bool stage_busy[2] = {false, false};
     int stage_next = 0;
-    IdxSlot* upload = nullptr;  // pinned: a rebuilt image on its way to the device
-    hipEvent_t update_ev = nullptr;
+    PinnedBuf<IdxSlot> upload;  // a rebuilt image on its way to the device
+    Event update_ev;
     hipStream_t update_stream = nullptr;
     bool update_pending = false;
 #endif
@@ -166,10 +166,10 @@ int idx_note_use(const neb_index_table* t, int k, hipStream_t s) {
             IDX_HIP(hipEventRecord(u.ev, s));
             return NEB_OK;
         }
-    hipEvent_t ev;
-    IDX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    t->uses[k].push_back(IdxUse{s, ev});
-    IDX_HIP(hipEventRecord(ev, s));
+    Event ev;
+    IDX_HIP(ev.create(hipEventDisableTiming));
+    t->uses[k].push_back(IdxUse{s, std::move(ev)});
+    IDX_HIP(hipEventRecord(t->uses[k].back().ev, s));
     return NEB_OK;
 }
 
@@ -215,13 +215,13 @@ int idx_push_update(neb_index_table* t, const std::map<uint32_t, bool>& fresh, c
 // The rebuilt host copy into the spare image, then the switch (mu held exclusively). Blocks.
 int idx_push_rebuild(neb_index_table* t, hipStream_t s) {
     int spare;
-    std::vector<IdxUse> waits;
+    std::vector<hipEvent_t> waits;
     {
         std::lock_guard<std::mutex> g(t->dmu);
         spare = t->active ^ 1;
-        waits = t->uses[spare];  // nothing new can start on the spare image
+        for (const IdxUse& u : t->uses[spare]) waits.push_back(u.ev);  // nothing new can start on the spare image
     }
-    for (const IdxUse& u : waits) IDX_HIP(hipEventSynchronize(u.ev));
+    for (hipEvent_t ev : waits) IDX_HIP(hipEventSynchronize(ev));
     const size_t bytes = t->slots.size() * sizeof(IdxSlot);
     std::memcpy(t->upload, t->slots.data(), bytes);
     IDX_HIP(hipMemcpyAsync(t->image[spare], t->upload, bytes, hipMemcpyHostToDevice, s));
@@ -232,36 +232,28 @@ int idx_push_rebuild(neb_index_table* t, hipStream_t s) {
     return NEB_OK;
 }
 
-void idx_free_device(neb_index_table* t) {
+// Waits for the device work on the table, then deletes it: its members release themselves
+// (hip_owned.hpp), with the table's device current.
+void idx_delete_device(neb_index_table* t) {
+    DeviceGuard dg(t->device);
     for (int k = 0; k < 2; k++) {
-        for (IdxUse& u : t->uses[k]) {
-            (void)hipEventSynchronize(u.ev);
-            (void)hipEventDestroy(u.ev);
-        }
-        if (t->stage_ev[k]) {
-            (void)hipEventSynchronize(t->stage_ev[k]);
-            (void)hipEventDestroy(t->stage_ev[k]);
-        }
-        if (t->stage[k]) (void)hipHostFree(t->stage[k]);
-        if (t->image[k]) (void)hipFree(t->image[k]);
+        for (IdxUse& u : t->uses[k]) (void)hipEventSynchronize(u.ev);
+        if (t->stage_ev[k]) (void)hipEventSynchronize(t->stage_ev[k]);
     }
-    if (t->update_ev) {
-        (void)hipEventSynchronize(t->update_ev);
-        (void)hipEventDestroy(t->update_ev);
-    }
-    if (t->upload) (void)hipHostFree(t->upload);
+    if (t->update_ev) (void)hipEventSynchronize(t->update_ev);
+    delete t;
 }
 
 int idx_init_device(neb_index_table* t) {
     const size_t bytes = t->slots.size() * sizeof(IdxSlot);
     for (int k = 0; k < 2; k++) {
-        IDX_HIP(hipMalloc((void**)&t->image[k], bytes));
+        IDX_HIP(t->image[k].reserve(bytes));
         IDX_HIP(hipMemset(t->image[k], 0, bytes));
-        IDX_HIP(hipHostMalloc((void**)&t->stage[k], kIdxStageOps * sizeof(IdxOp), hipHostMallocDefault));
-        IDX_HIP(hipEventCreateWithFlags(&t->stage_ev[k], hipEventDisableTiming));
+        IDX_HIP(t->stage[k].reserve(kIdxStageOps * sizeof(IdxOp)));
+        IDX_HIP(t->stage_ev[k].create(hipEventDisableTiming));
     }
-    IDX_HIP(hipHostMalloc((void**)&t->upload, bytes, hipHostMallocDefault));
-    IDX_HIP(hipEventCreateWithFlags(&t->update_ev, hipEventDisableTiming));
+    IDX_HIP(t->upload.reserve(bytes));
+    IDX_HIP(t->update_ev.create(hipEventDisableTiming));
     IDX_HIP(hipDeviceSynchronize());  // the images are zero before any stream reads them
     return NEB_OK;
 }
@@ -286,8 +278,7 @@ extern "C" NEB_API int neb_index_table_create(neb_engine* e, uint32_t capacity, 
         DeviceGuard dg(t->device);
         const int rc = idx_init_device(t);
         if (rc != NEB_OK) {
-            idx_free_device(t);
-            delete t;
+            idx_delete_device(t);
             return rc;
         }
     }
@@ -300,8 +291,8 @@ extern "C" NEB_API int neb_index_table_destroy(neb_index_table* t) {
     if (!t) return NEB_ERR_INVALID;
 #if defined(__HIPCC__)
     if (t->device >= 0) {
-        DeviceGuard dg(t->device);
-        idx_free_device(t);
+        idx_delete_device(t);
+        return NEB_OK;
     }
 #endif
     delete t;

@@ -21,13 +21,19 @@ struct HipDev {
     using Token = uint32_t;  // the staging batch's index (its stream)
     neb_engine* e = nullptr;
     int alg = 0, open = 0;
-    std::vector<hipStream_t> stream;
-    std::vector<SchedSpace*> sched;
+    struct Slot {  // of a staging batch: its stream and workspace, and what its arena, desc and status point at
+        neb::Stream stream;
+        SchedSpacePtr sched;
+        neb::PinnedBuf<> arena;
+        neb::PinnedBuf<neb_desc> desc;
+        neb::PinnedBuf<int32_t> status;
+    };
+    std::vector<Slot> slot;
     int launch(uint32_t i, neb_desc* desc, uint32_t n, uint8_t* arena, int32_t* status, uint32_t hint, Token& tok) {
         tok = i;
-        return neb_launch_on(e, alg, open, desc, n, arena, status, hint, stream[i], sched[i]);
+        return neb_launch_on(e, alg, open, desc, n, arena, status, hint, slot[i].stream, slot[i].sched.get());
     }
-    int wait(Token& tok) { return hipStreamSynchronize(stream[tok]) == hipSuccess ? NEB_OK : NEB_ERR_HIP; }
+    int wait(Token& tok) { return hipStreamSynchronize(slot[tok].stream) == hipSuccess ? NEB_OK : NEB_ERR_HIP; }
     bool key_ok(uint32_t key) { return neb_key_alg(e, key) == alg; }
     bool mapped(const uint8_t* arena) { return neb_host_mapped(arena); }
 };
@@ -44,35 +50,31 @@ NEB_API int neb_queue_create(neb_engine* e, int alg, int open, const neb_queue_c
     *out = nullptr;
     neb_queue_config c = cfg ? *cfg : neb_queue_config{};
     if (!neb_q::normalize(c)) return NEB_ERR_INVALID;
-    neb_queue* q = new (std::nothrow) neb_queue;
+    DeviceGuard dg(neb_engine_device_of(e));
+    std::unique_ptr<neb_queue> q(new (std::nothrow) neb_queue);  // (a failure below releases it under the guard)
     if (!q) return NEB_ERR_INVALID;
-    q->dev.e = e;
-    q->dev.alg = alg;
-    q->dev.open = open;
+    HipDev& dev = q->dev;
+    dev.e = e;
+    dev.alg = alg;
+    dev.open = open;
     q->open = open;
     q->cfg = c;
-    DeviceGuard dg(neb_engine_device_of(e));
     q->b.resize(c.depth);
-    q->dev.stream.assign(c.depth, nullptr);
-    q->dev.sched.assign(c.depth, nullptr);
-    bool ok = true;
+    dev.slot.resize(c.depth);
     for (uint32_t i = 0; i < c.depth; i++) {
-        ok = ok && hipStreamCreateWithFlags(&q->dev.stream[i], hipStreamNonBlocking) == hipSuccess;
-        q->dev.sched[i] = ok ? neb_sched_space_new() : nullptr;
-        ok = ok && q->dev.sched[i];
-    }
-    for (auto& x : q->b) {
-        ok = ok && hipHostMalloc((void**)&x.arena, c.arena_bytes, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&x.desc, (size_t)c.max_packets * sizeof(neb_desc), hipHostMallocDefault) ==
-                       hipSuccess;
-        ok = ok && hipHostMalloc((void**)&x.status, (size_t)c.max_packets * 4, hipHostMallocDefault) == hipSuccess;
-    }
-    if (!ok) {
-        neb_queue_destroy(q);
-        return NEB_ERR_HIP;
+        HipDev::Slot& st = dev.slot[i];
+        st.sched.reset(neb_sched_space_new());
+        if (st.stream.create(hipStreamNonBlocking) != hipSuccess || !st.sched ||
+            st.arena.reserve(c.arena_bytes) != hipSuccess ||
+            st.desc.reserve((size_t)c.max_packets * sizeof(neb_desc)) != hipSuccess ||
+            st.status.reserve((size_t)c.max_packets * 4) != hipSuccess)
+            return NEB_ERR_HIP;
+        q->b[i].arena = st.arena;
+        q->b[i].desc = st.desc;
+        q->b[i].status = st.status;
     }
     q->start();
-    *out = q;
+    *out = q.release();
     return NEB_OK;
 }
 
@@ -80,17 +82,9 @@ NEB_API int neb_queue_destroy(neb_queue* q) {
     if (!q) return NEB_ERR_INVALID;
     q->shutdown();
     DeviceGuard dg(neb_engine_device_of(q->dev.e));
-    for (hipStream_t st : q->dev.stream)
-        if (st) hipStreamSynchronize(st);
-    for (auto& x : q->b) {
-        if (x.arena) hipHostFree(x.arena);
-        if (x.desc) hipHostFree(x.desc);
-        if (x.status) hipHostFree(x.status);
-    }
-    for (SchedSpace* sp : q->dev.sched) neb_sched_space_free(sp);
-    for (hipStream_t st : q->dev.stream)
-        if (st) hipStreamDestroy(st);
-    delete q;
+    for (const HipDev::Slot& st : q->dev.slot)
+        if (st.stream) hipStreamSynchronize(st.stream);
+    delete q;  // each slot's staging, workspace and then stream release themselves (hip_owned.hpp)
     return NEB_OK;
 }
 

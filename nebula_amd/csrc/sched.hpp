@@ -149,3 +149,7 @@ __host__ __device__ inline uint32_t sched_max_chunks(uint32_t n, uint32_t max_ke
 // counts it reads, so a batch leaves them zero for the next).
 extern "C" hipError_t neb_sched_build(const neb_desc* d_desc, uint32_t n, const uint32_t* d_n, uint32_t max_keys,
                                       uint32_t lpp, const neb::SchedWs* ws, hipStream_t s);
+// A fenced shard's descriptors (engine.cpp KeyFence): `in` copied to `out` with the key_id of every
+// packet whose key slot is flagged in bad[0..nbad) pointing past every key table.
+extern "C" hipError_t neb_fence_keys(const neb_desc* in, neb_desc* out, uint32_t n, const uint8_t* bad, uint32_t nbad,
+                                     hipStream_t s);

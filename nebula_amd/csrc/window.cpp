@@ -44,7 +44,6 @@
 
 using namespace neb_rx;
 
-
 struct neb_window {
     WindowCore core;
     mutable std::mutex mu;  // ConnectionState.decryptLock (connection_state.go:100,112)
@@ -334,7 +333,6 @@ NEB_API int neb_rx_open_batch_host(neb_engine* e, int alg, neb_window* const* wi
     if (rc != NEB_OK) return rc;
     for (uint32_t i : commit) std::memcpy(arena + desc[i].dst_off, spec.data() + pt_at[i], desc[i].len);
     for (uint32_t i : zero) std::memset(arena + desc[i].dst_off, 0, desc[i].len);
-    if (rc != NEB_OK) return rc;
     if (prof)
         std::fprintf(stderr,
                      "rx n=%u threads %u/%u plan %.1f us (validate %.1f group %.1f split %.1f sim %.1f) stage+gpu %.1f "
@@ -351,29 +349,28 @@ NEB_API int neb_rx_open_batch_host(neb_engine* e, int alg, neb_window* const* wi
 struct neb_dwindows {
     neb_engine* e = nullptr;
     neb::RxDevWin win{};
-    uint8_t* mem = nullptr;
+    neb::DevBuf<> mem;
     std::mutex mu;  // one receive batch at a time on a window set
     // ws_mem and wire_mem need no event (workspace.hpp): the receive ends every batch with its stream
     // synchronized, so nothing is in flight in them when the next batch, on any stream, takes d->mu
-    uint8_t* ws_mem = nullptr;
-    size_t ws_bytes = 0;
+    neb::DevBuf<> ws_mem;
     neb::RxDevWs ws{};
     uint32_t ws_n = 0;
-    uint32_t* h_host = nullptr;  // pinned, mapped, 2 words (RxDevWs::need_host): a window needs the host; the scan failed
+    neb::MappedBuf<uint32_t> h_host;  // 2 words (RxDevWs::need_host): a window needs the host; the scan failed
     // neb_rx_open_wire_batch: descriptors + gate statuses; then neb_rx_open_via_batch's compaction
     // (WireMem below): arrival indices, compacted statuses, per-workgroup counts, two counter words
-    uint8_t* wire_mem = nullptr;
+    neb::DevBuf<> wire_mem;
     uint32_t wire_n = 0;
     uint32_t spin_limit = neb::kRxSpinLimit;  // neb_dwindows_set_spin_limit
-    SchedSpace* sched = nullptr;  // mixed-key AES-GCM receives: the open's scheduler workspace (rxwin.hpp RxBin)
+    SchedSpacePtr sched;  // mixed-key AES-GCM receives: the open's scheduler workspace (rxwin.hpp RxBin)
     // neb_relay_forward_batch: the forward half's workspace (relay.hpp), which runs on after the
     // call returns, and one pinned word for the single target tunnel's key
     neb::HipWorkspace<> relay;
     neb::RelayWs relay_ws{};
     uint32_t relay_n = 0, relay_tun = 0;
-    uint32_t* relay_key = nullptr;
+    neb::PinnedBuf<uint32_t> relay_key;
     // neb_rx_open_via_batch: one pinned, mapped word, the unwrap kernel's count of inner packets
-    uint32_t* via_count = nullptr;
+    neb::MappedBuf<uint32_t> via_count;
 };
 
 namespace {
@@ -426,7 +423,7 @@ NEB_API int neb_dwindows_create(neb_engine* e, uint32_t count, uint64_t length, 
         return NEB_ERR_INVALID;
     *out = nullptr;
     DeviceGuard dg(neb_engine_device_of(e));
-    neb_dwindows* d = new (std::nothrow) neb_dwindows;
+    std::unique_ptr<neb_dwindows> d(new (std::nothrow) neb_dwindows);
     if (!d) return NEB_ERR_INVALID;
     d->e = e;
     auto& v = d->win;
@@ -437,31 +434,19 @@ NEB_API int neb_dwindows_create(neb_engine* e, uint32_t count, uint64_t length, 
     while ((1u << v.words_lg) < v.words) v.words_lg++;
     const size_t b_present = neb::rx_align((size_t)count * 4), b_word = neb::rx_align((size_t)count * 8);
     const size_t bytes = b_present + 4 * b_word + (size_t)count * v.words * 8;
-    if (hipMalloc((void**)&d->mem, bytes) != hipSuccess || hipMemset(d->mem, 0, bytes) != hipSuccess ||
-        hipStreamSynchronize(nullptr) != hipSuccess) {
-        if (d->mem) hipFree(d->mem);
-        delete d;
-        return NEB_ERR_HIP;
-    }
-    if (hipHostMalloc((void**)&d->h_host, 2 * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) {
-        d->h_host = nullptr;
-        hipFree(d->mem);
-        delete d;
-        return NEB_ERR_HIP;
-    }
+    RX_HIP(d->mem.reserve(bytes));
+    RX_HIP(hipMemset(d->mem, 0, bytes));
+    RX_HIP(hipStreamSynchronize(nullptr));
+    RX_HIP(d->h_host.reserve(2 * sizeof(uint32_t)));
     uint8_t* m = d->mem;
-    v.present = (uint32_t*)m;
-    m += b_present;
-    v.cur = (uint64_t*)m;
-    m += b_word;
-    v.lost = (int64_t*)m;
-    m += b_word;
-    v.dupe = (int64_t*)m;
-    m += b_word;
-    v.oow = (int64_t*)m;
-    m += b_word;
+    auto take = [&m](size_t b) { return (m += b) - b; };  // the next b bytes
+    v.present = (uint32_t*)take(b_present);
+    v.cur = (uint64_t*)take(b_word);
+    v.lost = (int64_t*)take(b_word);
+    v.dupe = (int64_t*)take(b_word);
+    v.oow = (int64_t*)take(b_word);
     v.bits = (uint64_t*)m;
-    *out = d;
+    *out = d.release();
     return NEB_OK;
 }
 
@@ -472,16 +457,9 @@ NEB_API int neb_dwindows_destroy(neb_dwindows* d) {
         // neb_rx_open_batch returns only once its stream has run the batch, and holds d->mu
         // throughout: with the lock taken, nothing of this window set is in flight
         std::lock_guard<std::mutex> g(d->mu);
-        neb_sched_space_free(d->sched);
         d->relay.destroy();  // (waits: the forward half of the last relay batch may still be running)
-        if (d->relay_key) hipHostFree(d->relay_key);
-        if (d->via_count) hipHostFree(d->via_count);
-        if (d->ws_mem) hipFree(d->ws_mem);
-        if (d->wire_mem) hipFree(d->wire_mem);
-        if (d->mem) hipFree(d->mem);
-        if (d->h_host) hipHostFree(d->h_host);
     }
-    delete d;
+    delete d;  // with the engine's device current: the members release themselves (hip_owned.hpp)
     return NEB_OK;
 }
 
@@ -529,83 +507,14 @@ NEB_API int neb_dwindows_store(neb_dwindows* d, uint32_t idx, neb_window* w) {
 
 }  // extern "C"
 
-// neb_rx_open_batch with d->mu held (the wire form builds its descriptors under the same lock)
-static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const neb_desc* d_desc, uint32_t n,
-                                uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
+// The sequential finish of a device receive, for the windows the parallel one left (a tag failed, a
+// counter near its wrap, the spin limit hit; rare): exact_rounds replays their packets in arrival order
+// on host copies of the windows, opening in further device batches what it held back. d->mu held.
+static int rx_host_finish(neb_engine* e, int alg, neb_dwindows* d, const neb_desc* d_desc, uint32_t n,
+                          uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s) {
     int rc = NEB_OK;
-    hipSetDevice(neb_engine_device_of(e));
-    hipStream_t s = (hipStream_t)stream;
-    auto& v = d->win;
-    if (n > d->ws_n) {
-        const size_t bytes = neb::rx_ws_layout(n, v.count, v.words, nullptr, nullptr);
-        RX_HIP(hipStreamSynchronize(s));
-        if (d->ws_mem) hipFree(d->ws_mem);
-        d->ws_mem = nullptr;
-        d->ws_n = 0;
-        RX_HIP(hipMalloc((void**)&d->ws_mem, bytes));
-        neb::rx_ws_layout(n, v.count, v.words, d->ws_mem, &d->ws);
-
-        // the scratch bitmap is zeroed once here and again by each batch as it is consumed
-        RX_HIP(hipMemsetAsync(d->ws.scratch, 0, ((size_t)v.count << v.words_lg) * 8, s));
-        RX_HIP(hipMemsetAsync(d->ws.mixed, 0, 4, s));  // no generation is 0
-        d->ws.gen = UINT32_MAX;  // the first batch clears the first-occurrence table
-        d->ws_bytes = bytes;
-        d->ws_n = n;
-    }
-    // a new generation per batch empties the first-occurrence table; cleared for real at wrap
-    if (++d->ws.gen == 0) {  // (every generation-tagged word: the table, the block granules, wrisky)
-        const size_t nblk = ((size_t)d->ws_n + neb::kRxBlock - 1) / neb::kRxBlock;
-        RX_HIP(hipMemsetAsync(d->ws.tab_owner, 0, (size_t)8 << d->ws.tab_lg, s));
-        RX_HIP(hipMemsetAsync(d->ws.tab_min, 0, (size_t)8 << d->ws.tab_lg, s));
-        RX_HIP(hipMemsetAsync(d->ws.blk_pub, 0, nblk * 3 * 8, s));
-        RX_HIP(hipMemsetAsync(d->ws.wrisky, 0, (size_t)v.count * 4, s));
-        d->ws.gen = 1;
-    }
-    d->h_host[0] = d->h_host[1] = 0;
-    d->ws.need_host = d->h_host;
-    d->ws.spin_limit = d->spin_limit;
+    const auto& v = d->win;
     const neb::RxDevWs& ws = d->ws;
-
-    static const bool prof = std::getenv("NEB_RX_PROF") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    const auto t0 = now();
-    // Everything is queued at once, one host read at the end: windows whose counters come within
-    // 2^62 of wrapping hold all their packets back (admitted by none), and exact_rounds opens what
-    // their real pass accepts in batches, like the windows where a tag failed.
-    // 0. mixed-key AES-GCM: the open's binning (sched_body.hpp) reads only the descriptors, so extra
-    //    workgroups of the plan's own launches run it (rxwin.hpp RxBin): three launches off the chain.
-    //    A batch large enough for sub-bins is binned by the open itself.
-    SchedSpace* prebinned = nullptr;
-    neb::RxBin bin{};
-    if (alg == NEB_ALG_AESGCM && key_hint == NEB_KEYS_MIXED && (int64_t)n < neb::knob(NEB_KNOB_SUB_BINS_FROM)) {
-        if (!d->sched && !(d->sched = neb_sched_space_new())) return NEB_ERR_HIP;
-        if ((rc = neb_rx_sched_begin(e, n, d->sched, s, &bin.ws, &bin.max_keys)) != NEB_OK) return rc;
-        bin.on = 1;
-        prebinned = d->sched;
-    }
-    // 1. group by window, prefix maxima, first occurrences; admission for the safe windows
-    if (neb_rxdev_plan(d_desc, n, &v, &ws, d_status, &bin, s) != hipSuccess) {
-        if (prebinned) neb_rx_sched_abort(prebinned);
-        return NEB_ERR_HIP;
-    }
-    const auto t1 = now();
-    // 2. one open over the batch that runs the admitted packets only (the plan's mask), writing their
-    //    statuses at their arrival indices
-    rc = neb_open_batch_count(e, alg, d_desc, n, nullptr, d_arena, d_status, key_hint, s, ws.adm, prebinned);
-    if (rc != NEB_OK) return rc;
-    const auto t2 = now();
-    // 3. the verdicts into the windows, and the parallel finish of every window whose packets all verified
-    RX_HIP(neb_rxdev_finish(n, &v, &ws, d_status, s));
-    const auto t3 = now();
-    RX_HIP(hipStreamSynchronize(s));
-    if (prof)
-        std::fprintf(stderr, "rxdev n=%u enqueue plan %.1f, open %.1f, finish %.1f us, wait %.1f us\n", n, us(t0, t1),
-                     us(t1, t2), us(t2, t3), us(t3, now()));
-    // the plan and the open flag, in pinned host memory, whether any window needs the sequential finish
-    const uint32_t need = __atomic_load_n(d->h_host, __ATOMIC_ACQUIRE);
-    if (__atomic_load_n(d->h_host + 1, __ATOMIC_ACQUIRE)) return NEB_ERR_HIP;  // a scan lookback timed out
-    if (need == 0) return NEB_OK;
     std::vector<uint32_t> flag;
     if (d2h(flag, ws.wflag, v.count, s) != NEB_OK) return NEB_ERR_HIP;
     RX_HIP(hipStreamSynchronize(s));
@@ -645,7 +554,7 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
     });
     if (rc != NEB_OK) return rc;
     // speculative verifications: packets copied into a device scratch arena and opened there
-    uint8_t* d_spec = nullptr;
+    neb::DevBuf<> d_spec;
     std::vector<neb_desc> h_desc(n);
     std::vector<uint64_t> pt_at;
     std::vector<uint32_t> commit, zero;
@@ -653,12 +562,11 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
     RX_HIP(hipStreamSynchronize(s));
     auto run_spans = [&](const uint8_t* src, uint8_t* dst, const std::vector<neb_span>& sp) -> int {
         if (sp.empty()) return NEB_OK;
-        neb_span* d_sp = nullptr;
-        RX_HIP(hipMalloc((void**)&d_sp, sp.size() * sizeof(neb_span)));
+        neb::DevBuf<neb_span> d_sp;
+        RX_HIP(d_sp.reserve(sp.size() * sizeof(neb_span)));
         hipError_t err = hipMemcpyAsync(d_sp, sp.data(), sp.size() * sizeof(neb_span), hipMemcpyHostToDevice, s);
         if (err == hipSuccess) err = neb_rxdev_spans(src, dst, d_sp, (uint32_t)sp.size(), s);
         if (err == hipSuccess) err = hipStreamSynchronize(s);
-        hipFree(d_sp);
         return err == hipSuccess ? NEB_OK : NEB_ERR_HIP;
     };
     rc = exact_rounds(
@@ -699,18 +607,14 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
                 off += ((uint64_t)dd.len + 16 + 15) & ~15ull;
                 ds[j] = s2;
             }
-            if (d_spec) hipFree(d_spec);
-            d_spec = nullptr;
-            RX_HIP(hipMalloc((void**)&d_spec, off + 16));
+            d_spec.reset();  // (every round ends with s synchronized)
+            RX_HIP(d_spec.reserve(off + 16));
             int r = run_spans(d_arena, d_spec, sp);
             if (r != NEB_OK) return r;
-            neb_desc* d_ds = nullptr;
-            int32_t* d_st = nullptr;
-            RX_HIP(hipMalloc((void**)&d_ds, (size_t)cnt * sizeof(neb_desc)));
-            if (hipMalloc((void**)&d_st, (size_t)cnt * 4) != hipSuccess) {
-                hipFree(d_ds);
-                return NEB_ERR_HIP;
-            }
+            neb::DevBuf<neb_desc> d_ds;
+            neb::DevBuf<int32_t> d_st;
+            RX_HIP(d_ds.reserve((size_t)cnt * sizeof(neb_desc)));
+            RX_HIP(d_st.reserve((size_t)cnt * 4));
             std::vector<int32_t> st(cnt, NEB_STATUS_BAD_KEY);
             hipError_t err = hipMemcpyAsync(d_ds, ds.data(), (size_t)cnt * sizeof(neb_desc), hipMemcpyHostToDevice, s);
             r = err == hipSuccess ? neb_open_batch_count(e, alg, d_ds, cnt, nullptr, d_spec, d_st, key_hint, s, nullptr, nullptr)
@@ -718,8 +622,6 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
             if (r == NEB_OK && (hipMemcpyAsync(st.data(), d_st, (size_t)cnt * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
                                 hipStreamSynchronize(s) != hipSuccess))
                 r = NEB_ERR_HIP;
-            hipFree(d_ds);
-            hipFree(d_st);
             if (r != NEB_OK) return r;
             for (uint32_t j = 0; j < cnt; j++) {
                 adm[pk[j]] = 2;
@@ -738,43 +640,90 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
         rc = run_spans(d_spec, d_arena, back);
         if (rc == NEB_OK) rc = run_spans(nullptr, d_arena, zsp);
     }
-    if (d_spec) hipFree(d_spec);
     if (rc != NEB_OK) return rc;
     for (size_t r = 0; r < runs.size(); r++)
         if ((rc = dw_write(d, runs[r].w, cores[r])) != NEB_OK) return rc;
-    if (rc != NEB_OK) return rc;
     RX_HIP(hipMemcpyAsync(d_status, status.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     RX_HIP(hipStreamSynchronize(s));
     return NEB_OK;
 }
 
-static int rx_open_wire_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
-                             const neb_rx_packet* pk, uint32_t n, uint8_t* arena, size_t arena_len, int32_t* status,
-                             uint32_t key_hint, bool relayed);
+// neb_rx_open_batch with d->mu held (the wire form builds its descriptors under the same lock)
+static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const neb_desc* d_desc, uint32_t n,
+                                uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
+    int rc = NEB_OK;
+    hipSetDevice(neb_engine_device_of(e));
+    hipStream_t s = (hipStream_t)stream;
+    auto& v = d->win;
+    if (n > d->ws_n) {
+        d->ws_n = 0;
+        RX_HIP(d->ws_mem.reserve(neb::rx_ws_layout(n, v.count, v.words, nullptr, nullptr), nullptr,
+                                 [&] { return hipStreamSynchronize(s); }));
+        neb::rx_ws_layout(n, v.count, v.words, d->ws_mem, &d->ws);
 
-extern "C" {
+        // the scratch bitmap is zeroed once here and again by each batch as it is consumed
+        RX_HIP(hipMemsetAsync(d->ws.scratch, 0, ((size_t)v.count << v.words_lg) * 8, s));
+        RX_HIP(hipMemsetAsync(d->ws.mixed, 0, 4, s));  // no generation is 0
+        d->ws.gen = UINT32_MAX;  // the first batch clears the first-occurrence table
+        d->ws_n = n;
+    }
+    // a new generation per batch empties the first-occurrence table; cleared for real at wrap
+    if (++d->ws.gen == 0) {  // (every generation-tagged word: the table, the block granules, wrisky)
+        const size_t nblk = ((size_t)d->ws_n + neb::kRxBlock - 1) / neb::kRxBlock;
+        RX_HIP(hipMemsetAsync(d->ws.tab_owner, 0, (size_t)8 << d->ws.tab_lg, s));
+        RX_HIP(hipMemsetAsync(d->ws.tab_min, 0, (size_t)8 << d->ws.tab_lg, s));
+        RX_HIP(hipMemsetAsync(d->ws.blk_pub, 0, nblk * 3 * 8, s));
+        RX_HIP(hipMemsetAsync(d->ws.wrisky, 0, (size_t)v.count * 4, s));
+        d->ws.gen = 1;
+    }
+    d->h_host[0] = d->h_host[1] = 0;
+    d->ws.need_host = d->h_host;
+    d->ws.spin_limit = d->spin_limit;
+    const neb::RxDevWs& ws = d->ws;
 
-NEB_API int neb_rx_open_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_desc* d_desc, uint32_t n,
-                              uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
-    if (!e || !d || d->e != e || (n && (!d_desc || !d_arena || !d_status))) return NEB_ERR_INVALID;
-    int rc = neb_check_batch_args(e, alg, key_hint);
+    static const bool prof = std::getenv("NEB_RX_PROF") != nullptr;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const auto t0 = now();
+    // Everything is queued at once, one host read at the end: windows whose counters come within
+    // 2^62 of wrapping hold all their packets back (admitted by none), and exact_rounds opens what
+    // their real pass accepts in batches, like the windows where a tag failed.
+    // 0. mixed-key AES-GCM: the open's binning (sched_body.hpp) reads only the descriptors, so extra
+    //    workgroups of the plan's own launches run it (rxwin.hpp RxBin): three launches off the chain.
+    //    A batch large enough for sub-bins is binned by the open itself.
+    SchedSpace* prebinned = nullptr;
+    neb::RxBin bin{};
+    if (alg == NEB_ALG_AESGCM && key_hint == NEB_KEYS_MIXED && (int64_t)n < neb::knob(NEB_KNOB_SUB_BINS_FROM)) {
+        if (!d->sched) d->sched.reset(neb_sched_space_new());
+        if (!d->sched) return NEB_ERR_HIP;
+        if ((rc = neb_rx_sched_begin(e, n, d->sched.get(), s, &bin.ws, &bin.max_keys)) != NEB_OK) return rc;
+        bin.on = 1;
+        prebinned = d->sched.get();
+    }
+    // 1. group by window, prefix maxima, first occurrences; admission for the safe windows
+    if (neb_rxdev_plan(d_desc, n, &v, &ws, d_status, &bin, s) != hipSuccess) {
+        if (prebinned) neb_rx_sched_abort(prebinned);
+        return NEB_ERR_HIP;
+    }
+    const auto t1 = now();
+    // 2. one open over the batch that runs the admitted packets only (the plan's mask), writing their
+    //    statuses at their arrival indices
+    rc = neb_open_batch_count(e, alg, d_desc, n, nullptr, d_arena, d_status, key_hint, s, ws.adm, prebinned);
     if (rc != NEB_OK) return rc;
-    if (n == 0) return NEB_OK;
-    DeviceGuard dg;
-    std::lock_guard<std::mutex> g(d->mu);
-    return rx_open_batch_locked(e, alg, d, d_desc, n, d_arena, d_status, key_hint, stream);
+    const auto t2 = now();
+    // 3. the verdicts into the windows, and the parallel finish of every window whose packets all verified
+    RX_HIP(neb_rxdev_finish(n, &v, &ws, d_status, s));
+    const auto t3 = now();
+    RX_HIP(hipStreamSynchronize(s));
+    if (prof)
+        std::fprintf(stderr, "rxdev n=%u enqueue plan %.1f, open %.1f, finish %.1f us, wait %.1f us\n", n, us(t0, t1),
+                     us(t1, t2), us(t2, t3), us(t3, now()));
+    // the plan and the open flag, in pinned host memory, whether any window needs the sequential finish
+    const uint32_t need = __atomic_load_n(&d->h_host[0], __ATOMIC_ACQUIRE);
+    if (__atomic_load_n(&d->h_host[1], __ATOMIC_ACQUIRE)) return NEB_ERR_HIP;  // a scan lookback timed out
+    if (need == 0) return NEB_OK;
+    return rx_host_finish(e, alg, d, d_desc, n, d_arena, d_status, key_hint, s);
 }
-
-// readOutsidePackets' gate (neb_rx_wire_gate) on the host, then the batched receive over the
-// descriptors it builds; refused packets carry an empty descriptor with no key (untouched by the
-// receive) and get the gate's status.
-NEB_API int neb_rx_open_wire_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
-                                        const neb_rx_packet* pk, uint32_t n, uint8_t* arena, size_t arena_len,
-                                        int32_t* status, uint32_t key_hint) {
-    return rx_open_wire_host(e, alg, windows, nwindows, pk, n, arena, arena_len, status, key_hint, false);
-}
-
-}  // extern "C"
 
 // relayed: pk are the inner records of neb_rx_open_via_batch_host and status[] holds the unwrap's
 // marks: a record marked NEB_STATUS_NOT_RELAYED keeps that status, the others pass the gate with
@@ -801,6 +750,30 @@ static int rx_open_wire_host(neb_engine* e, int alg, neb_window* const* windows,
         if (gate[i] != NEB_STATUS_OK) status[i] = gate[i];
     return NEB_OK;
 }
+
+extern "C" {
+
+NEB_API int neb_rx_open_batch(neb_engine* e, int alg, neb_dwindows* d, const neb_desc* d_desc, uint32_t n,
+                              uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, void* stream) {
+    if (!e || !d || d->e != e || (n && (!d_desc || !d_arena || !d_status))) return NEB_ERR_INVALID;
+    int rc = neb_check_batch_args(e, alg, key_hint);
+    if (rc != NEB_OK) return rc;
+    if (n == 0) return NEB_OK;
+    DeviceGuard dg;
+    std::lock_guard<std::mutex> g(d->mu);
+    return rx_open_batch_locked(e, alg, d, d_desc, n, d_arena, d_status, key_hint, stream);
+}
+
+// readOutsidePackets' gate (neb_rx_wire_gate) on the host, then the batched receive over the
+// descriptors it builds; refused packets carry an empty descriptor with no key (untouched by the
+// receive) and get the gate's status.
+NEB_API int neb_rx_open_wire_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
+                                        const neb_rx_packet* pk, uint32_t n, uint8_t* arena, size_t arena_len,
+                                        int32_t* status, uint32_t key_hint) {
+    return rx_open_wire_host(e, alg, windows, nwindows, pk, n, arena, arena_len, status, key_hint, false);
+}
+
+}  // extern "C"
 
 // d->wire_mem carved for a capacity of n packets: the wire receive's descriptors and gate statuses,
 // then what neb_rx_open_via_batch's compacted phase 2 adds (the compacted batch's statuses and
@@ -835,11 +808,8 @@ static int rx_open_wire_locked(neb_engine* e, int alg, neb_dwindows* d, const ne
     int rc = NEB_OK;
     hipStream_t s = (hipStream_t)stream;
     if (n > d->wire_n) {
-        RX_HIP(hipStreamSynchronize(s));
-        if (d->wire_mem) hipFree(d->wire_mem);
-        d->wire_mem = nullptr;
         d->wire_n = 0;
-        RX_HIP(hipMalloc((void**)&d->wire_mem, WireMem::bytes(n)));
+        RX_HIP(d->wire_mem.reserve(WireMem::bytes(n), nullptr, [&] { return hipStreamSynchronize(s); }));
         d->wire_n = n;
         RX_HIP(hipMemsetAsync(WireMem(d->wire_mem, n).tot, 0, 8, s));  // zero between batches from here on
     }
@@ -860,7 +830,7 @@ static int rx_open_wire_locked(neb_engine* e, int alg, neb_dwindows* d, const ne
 
 // The forward half's workspace, grown as the receive's is (no allocation in the steady state).
 static int relay_reserve(neb_dwindows* d, uint32_t n, uint32_t ntun) {
-    if (!d->relay_key) RX_HIP(hipHostMalloc((void**)&d->relay_key, sizeof(uint32_t), hipHostMallocDefault));
+    RX_HIP(d->relay_key.reserve(sizeof(uint32_t)));
     if (d->relay.mem() && n <= d->relay_n && ntun <= d->relay_tun) return NEB_OK;
     const uint32_t nc = std::max({n, d->relay_n, 1024u}), tc = std::max({ntun, d->relay_tun, 64u});
     size_t cub = 0;
@@ -1008,12 +978,12 @@ NEB_API int neb_rx_open_via_batch(neb_engine* e, int alg, neb_dwindows* d, const
     std::lock_guard<std::mutex> g(d->mu);
     DeviceGuard dg(neb_engine_device_of(e));
     hipStream_t s = (hipStream_t)stream;
-    if (!d->via_count) RX_HIP(hipHostMalloc((void**)&d->via_count, sizeof(uint32_t), hipHostMallocMapped));
+    RX_HIP(d->via_count.reserve(sizeof(uint32_t)));
     *d->via_count = 0;
     const RxViaArgs via{d_via, d_inner_pk, d_inner_status};
     if ((rc = rx_open_wire_locked(e, alg, d, d_pk, n, d_arena, d_status, key_hint, stream, &via)) != NEB_OK) return rc;
     // no terminal relay packet verified: every inner_status is NEB_STATUS_NOT_RELAYED already
-    const uint32_t m = __atomic_load_n(d->via_count, __ATOMIC_ACQUIRE);
+    const uint32_t m = __atomic_load_n(&d->via_count[0], __ATOMIC_ACQUIRE);
     if (m == 0) return NEB_OK;
     if (m > n) return NEB_ERR_HIP;
     // phase 2 over the m inner packets, compacted in arrival order; phase 1 is done with wire_mem

@@ -5,11 +5,13 @@
 // s, end(s). Host-only logic over a device policy, like queue_core.hpp: the engine binds it to HIP
 // (HipWsApi below), tests/sanitize/workspace_test.cpp to a fake that logs the calls. Api has Stream,
 // Event, Error, kOk, event_create / _sync / _record / _destroy, stream_wait, stream_id (0 = the
-// runtime gives none), mem_alloc and mem_free.
+// runtime gives none), mem_alloc and mem_free; hip_owned.hpp's buffers add host_alloc and host_free.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+
+#include "hip_owned.hpp"
 
 namespace neb {
 
@@ -43,8 +45,8 @@ struct DevWorkspace {
     DevWorkspace& operator=(const DevWorkspace&) = delete;
     ~DevWorkspace() { destroy(); }
 
-    uint8_t* mem(int b = 0) const { return mem_[b]; }
-    size_t bytes(int b = 0) const { return bytes_[b]; }
+    uint8_t* mem(int b = 0) const { return buf_[b]; }
+    size_t bytes(int b = 0) const { return buf_[b].bytes(); }
     // `done`, for a batch that binds it to its last kernel's dispatch instead of end()'s marker
     // (then end_bound()); null before the first begin()
     typename Api::Event event() const { return done_; }
@@ -55,19 +57,11 @@ struct DevWorkspace {
     // allocation leaves it empty, capacity 0.
     Error reserve(size_t bytes, bool* grew = nullptr, int b = 0) {
         if (grew) *grew = false;
-        if (mem_[b] && bytes <= bytes_[b]) return Api::kOk;
-        Error err = sync();  // the old buffer may still be in use
+        if (buf_[b] && bytes <= buf_[b].bytes()) return Api::kOk;
+        const Error err = sync();  // the old buffer may still be in use
         if (err != Api::kOk) return err;
-        if (mem_[b]) Api::mem_free(mem_[b]);
-        mem_[b] = nullptr;
-        bytes_[b] = 0;
-        if ((err = Api::mem_alloc(&mem_[b], bytes)) != Api::kOk) {
-            mem_[b] = nullptr;
-            return err;
-        }
-        bytes_[b] = bytes;
-        if (grew) *grew = true;
-        return Api::kOk;
+        buf_[b].reset();
+        return buf_[b].reserve(bytes, grew);
     }
     // s waits for the last batch, unless that ran on s itself. `done` is created on first use,
     // ordering only (the host and other streams wait for the kernels, nobody reads the workspace
@@ -87,18 +81,13 @@ struct DevWorkspace {
             (void)Api::event_sync(done_);
             Api::event_destroy(done_);
         }
-        for (int b = 0; b < N; b++) {
-            if (mem_[b]) Api::mem_free(mem_[b]);
-            mem_[b] = nullptr;
-            bytes_[b] = 0;
-        }
+        for (auto& b : buf_) b.reset();
         done_ = {};
         last_ = {};
     }
 
   private:
-    uint8_t* mem_[N] = {};
-    size_t bytes_[N] = {};
+    OwnedBuf<Api> buf_[N];
     typename Api::Event done_{};
     StreamTag<Api> last_;  // the stream `done` was last recorded on
 };
@@ -131,6 +120,8 @@ struct HipWsApi {
     }
     static hipError_t mem_alloc(uint8_t** p, size_t bytes) { return hipMalloc((void**)p, bytes); }
     static void mem_free(uint8_t* p) { (void)hipFree(p); }
+    static hipError_t host_alloc(uint8_t** p, size_t bytes, unsigned flags) { return hipHostMalloc((void**)p, bytes, flags); }
+    static void host_free(uint8_t* p) { (void)hipHostFree(p); }
 };
 template <int N = 1>
 using HipWorkspace = DevWorkspace<HipWsApi, N>;

@@ -1,7 +1,8 @@
 """CPU: the engine's host logic under sanitizers — `make -C nebula_amd sanitize`
 builds window_core.hpp (replay window, exact receive rounds, thread pool) and queue_core.hpp (the
 submission queue, on a CPU device running the oracle) and workspace.hpp (the device workspaces'
-event and stream protocol, on a fake device that logs the calls) and pipe_core.hpp (the staged host
+event and stream protocol, on a fake device that logs the calls) and hip_owned.hpp (the owned
+buffers' growth, moves and release, on such a fake too) and pipe_core.hpp (the staged host
 pipeline's chunk plan, chunk spans and overlap test, against brute force) with ASan+UBSan and with
 TSan and runs them; the first two also check their results against the packet-by-packet receive /
 the oracle."""
@@ -22,3 +23,4 @@ def test_sanitizer_builds_run_clean():
     assert r.stdout.count("window_test: ok") == 2 and r.stdout.count("queue_test: ok") == 2, r.stdout
     assert r.stdout.count("workspace_test: ok") == 2, r.stdout
     assert r.stdout.count("pipe_test: ok") == 2, r.stdout
+    assert r.stdout.count("owned_test: ok") == 2, r.stdout
