@@ -748,6 +748,141 @@ NEB_API int neb_rx_resolve_batch(neb_engine* e, const neb_index_table* t, neb_rx
 NEB_API int neb_rx_resolve_batch_host(const neb_index_table* t, neb_rx_packet* pk, const neb_rx_source* src,
                                       uint32_t n, const uint8_t* arena, size_t arena_len, neb_relay_route* route,
                                       neb_rx_via* via);
+/* ---- TX resolve: parse, own-address gates and VPN address / route lookup for a TX batch -------- */
+/* The front half of consumeInsidePacket (inside.go:19-121) for a whole batch of TUN reads: newPacket
+ * (outside.go:320-472, iputil/packet.go:349-395), the local-broadcast, self and multicast gates
+ * (inside.go:43-76) and getOrHandshakeConsiderRouting (inside.go:292-372): Hosts[vpnAddr], the
+ * longest-prefix match over the unsafe routes (overlay/tun_linux.go:366-369) and ECMP
+ * (routing/balance.go, routing/gateway.go:57-70). Each is a pure function of the packet's first
+ * bytes over state that changes only at handshakes and config reloads, so the state lives in a table
+ * beside the tunnel array and one call fills neb_tx_packet.tunnel for neb_tx_seal_batch /
+ * neb_tx_seal_via_batch, and hands the caller's firewall its input (firewall.Packet). */
+#define NEB_STATUS_TX_DROPPED 10 /* a gate dropped the read (which one: neb_fw_packet.flags) */
+#define NEB_STATUS_NO_ROUTE 11   /* not in an own network and no route covers it (rejectInside) */
+#define NEB_STATUS_NO_TUNNEL 12  /* no host entry yet: the caller handshakes */
+#define NEB_TX_NO_TUNNEL 0xFFFFFFFFu /* neb_tx_packet.tunnel of a read that is not to be sealed */
+#define NEB_GATEWAY_NONE 0xFFFFFFFFu
+#define NEB_ROUTE_MAX_GATEWAYS 16
+#define NEB_TX_DROP_LOCAL_BROADCAST 1u /* f.dropLocalBroadcast */
+#define NEB_TX_DROP_MULTICAST 2u       /* f.dropMulticast */
+#define NEB_TX_KIND_HOST 0
+#define NEB_TX_KIND_ROUTE 1
+#define NEB_FW_FRAGMENT 0x01       /* ParsedPacket.Fragment: a non-first fragment, ports are 0 */
+#define NEB_FW_FRAG_ANY 0x02       /* ParsedPacket.FragAny: MF or an offset (v6: a fragment header) */
+#define NEB_FW_GATE_BROADCAST 0x04 /* dropped: an own IPv4 network's broadcast address */
+#define NEB_FW_GATE_SELF 0x08      /* dropped: one of the own VPN addresses */
+#define NEB_FW_GATE_MULTICAST 0x10 /* dropped: multicast */
+#define NEB_FW_ROUTED 0x20         /* a route was used: the tunnel is a gateway's */
+#define NEB_FW_ECMP_FALLBACK 0x40  /* the gateway ECMP chose has no tunnel; another one's was taken */
+typedef struct neb_tx_addr { /* a VPN address */
+    uint8_t addr[16];        /* family 4: the first 4 bytes, the rest is ignored */
+    uint8_t family /* 4 | 6; a 4-in-6 address is family 6 and never equals its IPv4 form */, reserved[3];
+} neb_tx_addr;
+typedef struct neb_tx_host { /* hostMap.Hosts[vpnAddr] (hostmap.go) */
+    neb_tx_addr addr;
+    uint32_t tunnel; /* index into the caller's neb_tx_tunnel array */
+} neb_tx_host;
+typedef struct neb_gateway { /* routing.Gateway */
+    neb_tx_addr addr;
+    uint32_t weight; /* used on a route of several gateways only */
+} neb_gateway;
+typedef struct neb_route { /* one unsafe route; the prefix's host bits are ignored, as bart's Insert does */
+    neb_cidr prefix;
+    uint32_t ngateways; /* 1..NEB_ROUTE_MAX_GATEWAYS */
+    neb_gateway gateways[NEB_ROUTE_MAX_GATEWAYS];
+} neb_route;
+/* firewall.ParsedPacket of an outgoing packet, and how the lookup went. 16-byte aligned. */
+typedef struct neb_fw_packet {
+    uint8_t local_addr[16];  /* family 4: the first 4 bytes, the rest 0 */
+    uint8_t remote_addr[16];
+    uint16_t local_port, remote_port; /* host order; ICMP / ICMPv6 echo: remote_port = identifier */
+    uint8_t protocol;
+    uint8_t family; /* 4 | 6 */
+    uint8_t flags;  /* NEB_FW_* */
+    uint8_t reserved;
+    uint16_t ip_hdr_len; /* ParsedPacket.IPHdrLen: where the upper protocol starts */
+    uint16_t reserved2;
+    uint32_t gateway; /* flat index, in neb_tx_table_set_routes order, of the gateway ECMP chose or of
+                         the single gateway; NEB_GATEWAY_NONE when no route was used */
+} neb_fw_packet;
+typedef struct neb_tx_table neb_tx_table;
+
+/* A table of at most host_capacity host entries, route_capacity routes and gateway_capacity
+ * gateways over all routes (fixed; host_capacity >= 1; each at most 2^20: NEB_ERR_INVALID beyond, and
+ * when the host copy, 128 to 256 bytes per host and route, cannot be allocated). e == NULL: a host-only
+ * table (neb_tx_resolve_batch_host only); otherwise the table also keeps its images in e's device
+ * memory. */
+NEB_API int neb_tx_table_create(neb_engine* e, uint32_t host_capacity, uint32_t route_capacity,
+                                uint32_t gateway_capacity, neb_tx_table** out);
+/* No call on the table may be in progress; waits for the device work the table has enqueued. */
+NEB_API int neb_tx_table_destroy(neb_tx_table* t);
+/* Host entries change with every handshake. The deletions in array order, then the puts in array
+ * order; a put of a live address replaces its tunnel; deleting an absent address is not an error.
+ * NEB_ERR_INVALID (nothing applied): a family other than 4 / 6, or the call's own bookkeeping
+ * could not be allocated. NEB_ERR_NO_KEY_SLOT (nothing
+ * applied): more than host_capacity entries would be live after the call. Thread-safe. Visibility
+ * is neb_index_table_update's: a resolve enqueued on `stream` after this call sees the update; a
+ * resolve running on another stream meanwhile sees, for every address, its tunnel from before or
+ * from after this call, never a mix, and never a miss for an address that is live before and after.
+ * Updates given on different streams take effect in the order of the calls. The call returns once
+ * its work is enqueued, except when the table compacts itself (deleted and replaced records have
+ * filled 3/4 of its slots): it then waits for every resolve that still reads the spare image, writes
+ * that image, waits for `stream`, and switches over. Meanwhile other updates, neb_tx_table_set_own
+ * and neb_tx_resolve_batch_host on this table wait for the call; neb_tx_resolve_batch does not: it
+ * goes on enqueueing resolves of the image that is still active. stream is ignored by a host-only
+ * table. */
+NEB_API int neb_tx_table_update_hosts(neb_tx_table* t, const neb_tx_addr* del, uint32_t ndel,
+                                      const neb_tx_host* put, uint32_t nput, void* stream);
+/* Routes change at a config reload only. Replaces the whole route set (nroutes == 0: none) through
+ * the compaction path above, so the call always blocks the calling thread until the spare image is
+ * written and switched to (who else waits meanwhile: as for a compaction above): every resolve sees
+ * one route set in its entirety, the new one if it was enqueued after the call returned, the old
+ * or the new one if it was enqueued while the call ran. A route of several gateways gets its ECMP
+ * buckets here (CalculateBucketsForGateways, routing/gateway.go:57-70). A gateway's tunnel is its
+ * host entry at resolve time, so a gateway's tunnel coming or going needs no route update.
+ * NEB_ERR_INVALID (nothing applied): ngateways == 0 or > NEB_ROUTE_MAX_GATEWAYS, a total weight of 0
+ * on a route of several gateways (the reference would divide by zero), a bad family or prefix
+ * length, two routes with the same masked prefix, or no memory for the new set. NEB_ERR_NO_KEY_SLOT (nothing applied): more
+ * than route_capacity routes or gateway_capacity gateways. */
+NEB_API int neb_tx_table_set_routes(neb_tx_table* t, const neb_route* routes, uint32_t nroutes, void* stream);
+/* The node's own networks (at most NEB_INDEX_MAX_NETWORKS), `addr` holding the node's own address in
+ * the network, unmasked (pki.go:475-487): gives the prefixes (myVpnNetworksTable), the own
+ * addresses (myVpnAddrsTable) and the IPv4 broadcast addresses network | ~mask
+ * (myVpnBroadcastAddrsTable). flags: NEB_TX_DROP_*. NEB_ERR_INVALID: more networks, a bad family or
+ * prefix length, unknown flags. Resolves called after this returns use the new set. */
+NEB_API int neb_tx_table_set_own(neb_tx_table* t, const neb_cidr* nets, uint32_t n, uint32_t flags);
+NEB_API int neb_tx_table_count(const neb_tx_table* t, uint32_t* hosts, uint32_t* routes);
+/* For tests, from the host copy: kind NEB_TX_KIND_HOST (key->bits ignored) or NEB_TX_KIND_ROUTE (the
+ * prefix is masked first); out = {found, slot, probes} as neb_index_table_probe. */
+NEB_API int neb_tx_table_probe(const neb_tx_table* t, uint32_t kind, const neb_cidr* key, uint32_t out[3]);
+/* Per TUN read i, the IP packet of packets[i].len bytes at packets[i].in_off (no alignment; nothing
+ * beyond those bytes is read):
+ *   newPacket(pkt, false, fp) fails: status NEB_STATUS_INVALID; fw[i] is zero but for ip_hdr_len and
+ *   NEB_FW_FRAG_ANY as newPacket had left them. Otherwise fw[i] is the ParsedPacket and
+ *   drop_local_broadcast and the remote address is an own IPv4 network's broadcast address, or
+ *   the remote address is an own address, or
+ *   drop_multicast and it is multicast (224.0.0.0/4, ff00::/8, a 4-in-6 address unmapped first, as
+ *   netip's IsMulticast does): NEB_STATUS_TX_DROPPED with that gate's NEB_FW_GATE_* flag;
+ *   the remote address is in an own network (netip.Prefix.Contains): its host entry gives the tunnel,
+ *   none is NEB_STATUS_NO_TUNNEL (routes are not consulted);
+ *   otherwise the longest route prefix containing it: none is NEB_STATUS_NO_ROUTE; else
+ *   NEB_FW_ROUTED, and with one gateway fw.gateway is that gateway; with several, h = hashPacket(
+ *   local_port, remote_port) and fw.gateway is the first with h <= its bucket's upper bound. Its
+ *   host entry gives the tunnel; without one, on a route of several gateways, the first gateway in
+ *   list order with another address and a host entry gives it (NEB_FW_ECMP_FALLBACK; fw.gateway
+ *   stays the chosen one); else NEB_STATUS_NO_TUNNEL.
+ * packets[i].tunnel is always written: the tunnel on NEB_STATUS_OK, else NEB_TX_NO_TUNNEL, which a
+ * following neb_tx_seal_batch / neb_tx_seal_via_batch on the same stream answers with
+ * NEB_STATUS_BAD_KEY, no wire and no counter. On NEB_STATUS_NO_TUNNEL the caller handshakes with
+ * remote_addr when fw.gateway is NEB_GATEWAY_NONE, else with that gateway's address. d_fw (16-byte
+ * aligned) and d_status may be NULL: not written. Only enqueues one kernel on `stream`.
+ * NEB_ERR_INVALID for a host-only table. */
+NEB_API int neb_tx_resolve_batch(neb_engine* e, const neb_tx_table* t, neb_tx_packet* d_packets, uint32_t npackets,
+                                 const uint8_t* d_in, neb_fw_packet* d_fw, int32_t* d_status, void* stream);
+/* The same over host memory, from the table's host copy (any table). Every packet is checked
+ * against in_len first (NEB_ERR_INVALID: nothing written). */
+NEB_API int neb_tx_resolve_batch_host(const neb_tx_table* t, neb_tx_packet* packets, uint32_t npackets,
+                                      const uint8_t* in, size_t in_len, neb_fw_packet* fw, int32_t* status);
 /* ---- submission queue: many threads' small flushes -> device-sized batches -------------------- */
 /* Nebula seals <= 128 packets per TX flush (overlay/batch/tx_batch.go:5, flushSendBatch
  * interface.go:465-487) and opens <= listen.batch = 64 per RX flush (main.go:181, listenOut

@@ -38,6 +38,9 @@ STATUS_NO_SPACE = 6
 STATUS_NOT_MESSAGE = 7
 STATUS_NOT_FORWARDED = 8  # relay forwarding: not a verified Message/Relay packet, or no route
 STATUS_NOT_RELAYED = 9  # neb_rx_open_via_batch's inner_status: not a verified terminal relay packet
+STATUS_TX_DROPPED = 10  # neb_tx_resolve_batch: a gate dropped the read (FW_GATE_* says which)
+STATUS_NO_ROUTE = 11  # neb_tx_resolve_batch: not in an own network and no route
+STATUS_NO_TUNNEL = 12  # neb_tx_resolve_batch: no host entry yet, the caller handshakes
 
 OVERHEAD = 16
 HEADER_LEN = 16
@@ -78,6 +81,25 @@ assert INDEX_ENTRY_DTYPE.itemsize == 24
 CIDR_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("bits", "u1"), ("reserved", "u1", (2,))])
 RX_SOURCE_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("reserved", "u1", (3,))])
 assert CIDR_DTYPE.itemsize == 20 and RX_SOURCE_DTYPE.itemsize == 20
+
+# neb_tx_table_* (include/nebula_aead.h): the TX-side lookups (VPN address -> tunnel, routes, ECMP)
+TX_NO_TUNNEL = 0xFFFFFFFF
+GATEWAY_NONE = 0xFFFFFFFF
+ROUTE_MAX_GATEWAYS = 16
+TX_DROP_LOCAL_BROADCAST, TX_DROP_MULTICAST = 1, 2
+TX_KIND_HOST, TX_KIND_ROUTE = 0, 1
+FW_FRAGMENT, FW_FRAG_ANY, FW_GATE_BROADCAST, FW_GATE_SELF, FW_GATE_MULTICAST = 0x01, 0x02, 0x04, 0x08, 0x10
+FW_ROUTED, FW_ECMP_FALLBACK = 0x20, 0x40
+TX_ADDR_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("reserved", "u1", (3,))])
+TX_HOST_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("reserved", "u1", (3,)), ("tunnel", "<u4")])
+GATEWAY_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("reserved", "u1", (3,)), ("weight", "<u4")])
+ROUTE_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("bits", "u1"), ("reserved", "u1", (2,)),
+                        ("ngateways", "<u4"), ("gateways", GATEWAY_DTYPE, (ROUTE_MAX_GATEWAYS,))])
+FW_PACKET_DTYPE = np.dtype([("local_addr", "u1", (16,)), ("remote_addr", "u1", (16,)), ("local_port", "<u2"),
+                            ("remote_port", "<u2"), ("protocol", "u1"), ("family", "u1"), ("flags", "u1"),
+                            ("reserved", "u1"), ("ip_hdr_len", "<u2"), ("reserved2", "<u2"), ("gateway", "<u4")])
+assert TX_ADDR_DTYPE.itemsize == 20 and TX_HOST_DTYPE.itemsize == 24
+assert GATEWAY_DTYPE.itemsize == 24 and ROUTE_DTYPE.itemsize == 408 and FW_PACKET_DTYPE.itemsize == 48
 
 # neb_plain_packet (include/nebula_aead.h): one MultiCoalescer.Commit
 PLAIN_PARSED, PLAIN_FRAG_ANY, PLAIN_SKIP = 1, 2, 4
@@ -167,6 +189,15 @@ SIGNATURES = {
     "neb_index_table_probe": (_i, [_vp, _u32, _u32, C.POINTER(_u32)]),
     "neb_rx_resolve_batch": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "neb_rx_resolve_batch_host": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
+    "neb_tx_table_create": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "neb_tx_table_destroy": (_i, [_vp]),
+    "neb_tx_table_update_hosts": (_i, [_vp, _vp, _u32, _vp, _u32, _vp]),
+    "neb_tx_table_set_routes": (_i, [_vp, _vp, _u32, _vp]),
+    "neb_tx_table_set_own": (_i, [_vp, _vp, _u32, _u32]),
+    "neb_tx_table_count": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "neb_tx_table_probe": (_i, [_vp, _u32, _vp, C.POINTER(_u32)]),
+    "neb_tx_resolve_batch": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "neb_tx_resolve_batch_host": (_i, [_vp, _vp, _u32, _vp, _sz, _vp, _vp]),
     "neb_seal_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_open_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_seal_batch_sharded": (_i, [_i, _vp, _u32, _u32]),

@@ -3,7 +3,12 @@ include/nebula_aead.h): what readOutsidePackets looks up per datagram before it 
 tunnel of the header's remote index (outside.go:93-106, hostmap.go:546-577), the double-encryption
 check on the UDP source (outside.go:66-74) and a relay's type and target (outside.go:201-240) — for
 a whole receive batch in one call, in front of rx_open_wire_batch, relay_forward_batch and
-rx_open_via_batch."""
+rx_open_via_batch.
+
+And its TX-side lookups (neb_tx_table_*, neb_tx_resolve_batch[_host]): what consumeInsidePacket does
+per TUN read before it can send (inside.go:19-121) — newPacket, the broadcast, self and multicast
+gates, Hosts[vpnAddr], the unsafe routes' longest-prefix match and ECMP — for a whole TX batch in
+one call, in front of neb_tx_seal_batch / neb_tx_seal_via_batch (TxTable)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -136,4 +141,141 @@ class IndexTable:
         return torch.cuda.current_stream().cuda_stream
 
 
-__all__ = ["IndexTable", "entries", "sources"]
+def _addr_into(rec, a: str) -> None:
+    ip = ipaddress.ip_address(a)
+    rec["family"] = ip.version
+    rec["addr"][:len(ip.packed)] = np.frombuffer(ip.packed, np.uint8)
+
+
+def tx_addrs(addrs: Sequence[str]) -> np.ndarray:
+    """VPN addresses -> TX_ADDR_DTYPE ("::ffff:a.b.c.d" stays a 16-byte address of family 6)."""
+    out = np.zeros(len(addrs), L.TX_ADDR_DTYPE)
+    for k, a in enumerate(addrs):
+        _addr_into(out[k], a)
+    return out
+
+
+def tx_hosts(rows: Iterable[Tuple[str, int]]) -> np.ndarray:
+    """[(VPN address, tunnel index)] -> TX_HOST_DTYPE"""
+    rows = list(rows)
+    out = np.zeros(len(rows), L.TX_HOST_DTYPE)
+    for k, (a, tunnel) in enumerate(rows):
+        _addr_into(out[k], a)
+        out[k]["tunnel"] = tunnel
+    return out
+
+
+def tx_routes(rows: Iterable[Tuple[str, Sequence[Tuple[str, int]]]]) -> np.ndarray:
+    """[(prefix, [(gateway address, weight)])] -> ROUTE_DTYPE"""
+    rows = list(rows)
+    out = np.zeros(len(rows), L.ROUTE_DTYPE)
+    for k, (prefix, gws) in enumerate(rows):
+        n = ipaddress.ip_network(prefix, strict=False)
+        _addr_into(out[k], str(n.network_address))
+        out[k]["bits"], out[k]["ngateways"] = n.prefixlen, len(gws)
+        for j, (a, weight) in enumerate(gws[:L.ROUTE_MAX_GATEWAYS]):
+            _addr_into(out[k]["gateways"][j], a)
+            out[k]["gateways"][j]["weight"] = weight
+    return out
+
+
+def tx_own(networks: Sequence[str]) -> np.ndarray:
+    """Own networks such as "10.1.0.7/16" (the node's own address with the network's length) ->
+    CIDR_DTYPE, the address unmasked."""
+    out = np.zeros(len(networks), L.CIDR_DTYPE)
+    for k, s in enumerate(networks):
+        i = ipaddress.ip_interface(s)
+        _addr_into(out[k], str(i.ip))
+        out[k]["bits"] = i.network.prefixlen
+    return out
+
+
+class TxTable:
+    """One neb_tx_table: VPN address -> tunnel, the unsafe routes with their ECMP gateways, and the
+    own networks of the TX gates. engine=None: host-only (resolve_host only)."""
+
+    def __init__(self, engine, hosts: int, routes: int = 0, gateways: int = 0):
+        self.engine = engine
+        self.handle = C.c_void_p()
+        L.check(L.lib().neb_tx_table_create(engine.handle if engine is not None else None, hosts, routes, gateways,
+                                            C.byref(self.handle)), "neb_tx_table_create")
+
+    def close(self) -> None:
+        if self.handle:
+            L.lib().neb_tx_table_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def update_hosts(self, delete: Sequence[str] = (), put=(), stream=None) -> None:
+        """delete: addresses, applied first; put: TX_HOST_DTYPE or rows for tx_hosts(). With an
+        engine the device image follows on `stream` (torch's current one by default)."""
+        dl = tx_addrs(list(delete))
+        pt = put if isinstance(put, np.ndarray) else tx_hosts(put)
+        pt = np.ascontiguousarray(pt, dtype=L.TX_HOST_DTYPE)
+        L.check(L.lib().neb_tx_table_update_hosts(self.handle, _vp(dl), len(dl), _vp(pt), len(pt),
+                                                  C.c_void_p(self._stream(stream))), "neb_tx_table_update_hosts")
+
+    def set_routes(self, routes=(), stream=None) -> None:
+        """routes: ROUTE_DTYPE or rows for tx_routes(); replaces the whole set. Blocks."""
+        rt = routes if isinstance(routes, np.ndarray) else tx_routes(routes)
+        rt = np.ascontiguousarray(rt, dtype=L.ROUTE_DTYPE)
+        L.check(L.lib().neb_tx_table_set_routes(self.handle, _vp(rt), len(rt), C.c_void_p(self._stream(stream))),
+                "neb_tx_table_set_routes")
+
+    def set_own(self, networks: Sequence[str], drop_local_broadcast: bool = False, drop_multicast: bool = False) -> None:
+        nets = tx_own(networks)
+        flags = (L.TX_DROP_LOCAL_BROADCAST if drop_local_broadcast else 0) | (L.TX_DROP_MULTICAST if drop_multicast else 0)
+        L.check(L.lib().neb_tx_table_set_own(self.handle, _vp(nets), len(nets), flags), "neb_tx_table_set_own")
+
+    def count(self) -> Tuple[int, int]:
+        """(host entries, routes)"""
+        h, r = C.c_uint32(), C.c_uint32()
+        L.check(L.lib().neb_tx_table_count(self.handle, C.byref(h), C.byref(r)), "neb_tx_table_count")
+        return h.value, r.value
+
+    def probe(self, key: str, route: bool = False) -> Tuple[bool, int, int]:
+        """(found, slot, probes) from the host copy; key: an address, or a prefix when route."""
+        c = np.zeros(1, L.CIDR_DTYPE)
+        n = ipaddress.ip_network(key, strict=False)
+        _addr_into(c[0], str(n.network_address))
+        c[0]["bits"] = n.prefixlen
+        out = (C.c_uint32 * 3)()
+        L.check(L.lib().neb_tx_table_probe(self.handle, L.TX_KIND_ROUTE if route else L.TX_KIND_HOST, _vp(c), out),
+                "neb_tx_table_probe")
+        return bool(out[0]), out[1], out[2]
+
+    def resolve_host(self, packets: np.ndarray, arena: np.ndarray, arena_len: Optional[int] = None, want_fw: bool = True):
+        """neb_tx_resolve_batch_host. packets: inside.TX_PACKET_DTYPE, contiguous; tunnel is written
+        in place. Returns (fw or None, status), allocated per call: a caller that times the host
+        form calls the C entry point on arrays of its own (tools/tx_resolve_bench.py)."""
+        from .inside import TX_PACKET_DTYPE
+
+        if packets.dtype != TX_PACKET_DTYPE or not packets.flags.c_contiguous:
+            raise ValueError("packets: a contiguous TX_PACKET_DTYPE array (updated in place)")
+        n = len(packets)
+        fw = np.zeros(n, L.FW_PACKET_DTYPE) if want_fw else None
+        status = np.zeros(n, np.int32)
+        rc = L.lib().neb_tx_resolve_batch_host(self.handle, _vp(packets), n, _vp(arena),
+                                               arena.nbytes if arena_len is None else arena_len, _vp(fw), _vp(status))
+        L.check(rc, "neb_tx_resolve_batch_host")
+        return fw, status
+
+    def resolve_device(self, d_packets, d_in, d_fw=None, d_status=None, stream=None) -> None:
+        """neb_tx_resolve_batch with everything in device memory (torch uint8 tensors of
+        TX_PACKET_DTYPE / FW_PACKET_DTYPE records, an int32 tensor of statuses). Only enqueues: the
+        outputs are valid for later work on the same stream."""
+        n = d_packets.numel() // 32
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        rc = L.lib().neb_tx_resolve_batch(self.engine.handle if self.engine is not None else None, self.handle,
+                                          p(d_packets), n, p(d_in), p(d_fw), p(d_status), C.c_void_p(self._stream(stream)))
+        L.check(rc, "neb_tx_resolve_batch")
+
+    _stream = IndexTable._stream
+
+
+__all__ = ["IndexTable", "entries", "sources", "TxTable", "tx_addrs", "tx_hosts", "tx_routes", "tx_own"]
