@@ -919,8 +919,9 @@ struct GhChunkTail {
 // words as it encrypts them. The field's block was encrypted with the partial (round 0): the
 // packet's last lane then stores the field's final ciphertext bytes and moves the tag by the
 // change, S' = S ^ Δ·H^e (GHASH is linear; e = n + 1 - the field block's index), with the Shoup
-// tables of H^(2^j), j < 10, in LDS (e < 1024: segments under 16 KB).
-// desc.flags = hdr | field << 12 | kind << 24 | parity << 26 (kind 1: TCP or a plain packet, 2:
+// tables of H^(2^j), j < 10, in LDS (e < 1024: tx.hip's seal_cs admits no other segment; under
+// 16 KB alone is not enough, a field in block 0 or 1 of 1024 blocks has e = 1025 or 1024).
+// desc.flags = hdr | field << 12 | kind << 24 | parity << 26, or hdr alone (kind 1: TCP or a plain packet, 2:
 // UDP, whose computed zero goes out as 0xFFFF; parity: the checksum start's, for the word pairing).
 constexpr uint32_t kCsHdrMask = 0xFFFu;
 __device__ __forceinline__ uint32_t le16_sum(uint4 v) {
@@ -1016,7 +1017,8 @@ __device__ __forceinline__ void gcm_packet_group(const GcmArgs& args, uint32_t p
     if (!key_ok || d.key_id != expect_key) st = NEB_STATUS_BAD_KEY;
     if (!OPEN && st == NEB_STATUS_OK && d.counter >= kRejectAfterMessages) st = NEB_STATUS_EXHAUSTED;
     const bool run = valid && st == NEB_STATUS_OK;
-    const uint32_t hdr = args.hdr_from_dst ? d.flags & kCsHdrMask : 0u;
+    // (no checksum kind: the whole word is the prefix, a plain packet's can pass 12 bits)
+    const uint32_t hdr = !args.hdr_from_dst ? 0u : ((d.flags >> 24) & 3u) ? d.flags & kCsHdrMask : d.flags;
     // CS: this lane's payload word sum, and (the field's lane) partial << 16 | keystream bytes
     uint32_t cs_acc = 0, cs_fk = 0;
     const bool cs_on = CS && !OPEN && ((d.flags >> 24) & 3u) != 0u;

@@ -640,6 +640,8 @@ constexpr int kTxWaves = 4;
 #define NEB_TX_MINBLOCKS 4
 #endif
 constexpr uint32_t kTxGroup = NEB_TX_GROUP;        // lanes per segment: 64 / kTxGroup segments per wave
+// the longest plaintext prefix a seal descriptor's flags can name beside a checksum field (aes_gcm.hip kCsHdrMask)
+constexpr uint32_t kTxMaxPrefix = 0xFFFu;
 constexpr uint32_t kTxRegUnits = NEB_TX_REGUNITS;  // payload units per lane kept in registers (16 x 6 x 16 B = 1.5 KiB)
 
 __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
@@ -711,11 +713,16 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
         // an exhausted one keeps only its header
         const bool work = live && counter < kRejectAfterMessages && !outer_dead;
         // the seal's checksum: the field inside one 16-B block and inside the prefix the seal reads
-        // from the slot, the payload words paired like the checksum start's, e < 1024
+        // from the slot, the payload words paired like the checksum start's, and the tag's correction
+        // within the seal's tables: e = payload blocks + 1 - the field's block < 1024 (a 16383-byte
+        // segment has 1024 blocks: its field must lie in block 2 or later)
         const uint32_t fld = gsok ? (plan.kind == kTxTcp ? cs + 16u : cs + 6u) : cs + co;
         const uint32_t hdr_b = gsok ? hl : plan.kind == kTxFinish ? cs + co + 2u : 0u;
-        const bool seal_cs = work && s < cs_p0 && plan.kind != kTxPass && (fld & 15u) != 15u &&
-                             ((hdr_b - cs) & 1u) == 0u && fld + 2u <= hdr_b && seg_len < 16384u;
+        // (a longer prefix does not fit beside the field in the descriptor's flags: no kind, the whole
+        // word is the prefix length)
+        const bool seal_cs = work && s < cs_p0 && plan.kind != kTxPass && hdr_b <= kTxMaxPrefix && (fld & 15u) != 15u &&
+                             ((hdr_b - cs) & 1u) == 0u && fld + 2u <= hdr_b && seg_len < 16384u &&
+                             ((seg_len + 15u) >> 4) + 1u - (fld >> 4) < 1024u;
 
         if (live && g == 0) {
             wires[s] = neb_tx_wire{slot, counter, seg_len + 32u + 2u * vo, p, j, vo ? (uint32_t)NEB_TX_WIRE_VIA : 0u};
