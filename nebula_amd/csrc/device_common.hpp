@@ -138,4 +138,14 @@ __device__ __forceinline__ void one_publish_status(int32_t* host_status, const i
     if (__lane_id() == 0) __hip_atomic_store(host_status, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// A word of a lookup table's device image (resolve.hip, route.hip): an 8-byte agent-scope atomic
+// load, served by the L2 and never by a CU's L1.
+struct LoadAgent {
+    __device__ __forceinline__ uint64_t operator()(const uint64_t* p) const {
+        const uint64_t v = __hip_atomic_load(const_cast<uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the loads in program order
+        return v;
+    }
+};
+
 }  // namespace neb

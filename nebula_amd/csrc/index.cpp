@@ -1,8 +1,7 @@
 // index.cpp — neb_index_table_* and neb_rx_resolve_batch[_host]: the table of the hostmap's
 // receive-side index lookups (rules: index_core.hpp). The host copy is authoritative: every update
 // is applied to it first, under the table's lock, and neb_rx_resolve_batch_host reads it. A table
-// made with an engine also keeps two images in device memory: the active one is brought up to date
-// by a scatter kernel on the caller's stream (resolve.hip), the spare one takes the next rebuild.
+// made with an engine also keeps a device copy (table_mirror.hpp), written by resolve.hip's scatter.
 // Compiled without HIP (g++: tests/sanitize_index) only the host-only table exists.
 #include <algorithm>
 #include <cstring>
@@ -15,6 +14,7 @@
 #include <vector>
 
 #include "index_core.hpp"
+#include "table_mirror.hpp"
 
 #if defined(__HIPCC__)
 #include "engine_internal.hpp"
@@ -27,18 +27,12 @@ using namespace neb;
 namespace {
 
 constexpr uint32_t kIdxMaxCapacity = 1u << 24;
-#if defined(__HIPCC__)
-constexpr uint32_t kIdxStageOps = 4096;  // ops per scatter launch (two pinned staging buffers)
 
-struct IdxUse {  // the last work a stream has enqueued on an image
-    hipStream_t s;
-    neb::Event ev;
+struct IdxTouch {  // one key an update names
+    bool live;      // is it live now
+    int32_t fresh;  // the slot this call filled for it, as an index into `fresh`, or -1
 };
-#endif
-
-struct IdxHostLoad {
-    uint64_t operator()(const uint64_t* p) const { return *p; }
-};
+using IdxRecs = std::map<uint64_t, std::pair<uint64_t, uint64_t>>;  // tag -> a, b
 
 }  // namespace
 
@@ -51,26 +45,15 @@ struct neb_index_table {
     IdxNets nets{};
 #if defined(__HIPCC__)
     int device = -1;  // -1: host-only
-    // dmu: which image is active, and the events (taken inside mu by writers, alone by resolves)
-    mutable std::mutex dmu;
-    DevBuf<IdxSlot> image[2];
-    int active = 0;
-    mutable std::vector<IdxUse> uses[2];
-    PinnedBuf<IdxOp> stage[2];
-    Event stage_ev[2];
-    bool stage_busy[2] = {false, false};
-    int stage_next = 0;
-    PinnedBuf<IdxSlot> upload;  // a rebuilt image on its way to the device
-    Event update_ev;
-    hipStream_t update_stream = nullptr;
-    bool update_pending = false;
+    // the device copy; its lock is taken inside mu by writers, alone by the resolve's launch
+    TableMirror<HipWsApi, IdxSlot, IdxOp> dev;
 #endif
 };
 
 namespace {
 
 inline bool idx_find_host(const neb_index_table* t, uint32_t space, uint32_t index, uint32_t* slot, uint32_t* probes) {
-    return idx_find(t->slots.data(), t->mask, space, index, IdxHostLoad{}, slot, probes);
+    return idx_find(t->slots.data(), t->mask, space, index, HostLoad{}, slot, probes);
 }
 
 // The first EMPTY slot of a key's chain (the table always has one).
@@ -92,59 +75,49 @@ int idx_validate(const neb_index_key* del, uint32_t ndel, const neb_index_entry*
     return NEB_OK;
 }
 
-// Entries live after the call: the deletions, then the puts, over the keys the call names.
-uint64_t idx_live_after(const neb_index_table* t, const neb_index_key* del, uint32_t ndel, const neb_index_entry* put,
-                        uint32_t nput) {
-    std::unordered_map<uint64_t, bool> now;
-    int64_t delta = 0;
-    auto touch = [&](uint32_t space, uint32_t index, bool to) {
-        const uint64_t tag = idx_tag(space, index);
-        auto it = now.find(tag);
-        if (it == now.end()) {
-            uint32_t s, p;
-            it = now.emplace(tag, idx_find_host(t, space, index, &s, &p)).first;
-        }
-        delta += (int)to - (int)it->second;
-        it->second = to;
-    };
-    for (uint32_t i = 0; i < ndel; i++) touch(del[i].space, del[i].index, false);
-    for (uint32_t i = 0; i < nput; i++) touch(put[i].space, put[i].index, true);
-    return (uint64_t)((int64_t)t->live + delta);
-}
-
 // The update on the host copy, slot by slot. fresh: the slots it filled, and whether each is still
-// live at the end; dead: the slots live before the call that it tombstoned.
+// live at the end; dead: the slots live before the call that it tombstoned. Allocates nothing: the
+// caller has reserved fresh and dead, and `now` holds every key the call names.
 void idx_apply(neb_index_table* t, const neb_index_key* del, uint32_t ndel, const neb_index_entry* put, uint32_t nput,
-               std::map<uint32_t, bool>* fresh, std::vector<uint32_t>* dead) {
-    auto bury = [&](uint32_t s) {
+               std::unordered_map<uint64_t, IdxTouch>* now, std::vector<std::pair<uint32_t, bool>>* fresh,
+               std::vector<uint32_t>* dead) {
+    auto bury = [&](uint32_t s, IdxTouch* tc) {
         t->slots[s].tag = kIdxTomb;
         t->live--;
-        auto it = fresh->find(s);
-        if (it != fresh->end()) it->second = false;
+        if (tc->fresh >= 0) (*fresh)[(size_t)tc->fresh].second = false;
         else dead->push_back(s);
+        tc->fresh = -1;
     };
     uint32_t s, p;
     for (uint32_t i = 0; i < ndel; i++)
-        if (idx_find_host(t, del[i].space, del[i].index, &s, &p)) bury(s);
+        if (idx_find_host(t, del[i].space, del[i].index, &s, &p)) bury(s, &now->find(idx_tag(del[i].space, del[i].index))->second);
     for (uint32_t i = 0; i < nput; i++) {
+        IdxTouch* tc = &now->find(idx_tag(put[i].space, put[i].index))->second;
         const bool had = idx_find_host(t, put[i].space, put[i].index, &s, &p);
         const uint32_t to = idx_free_slot(t, put[i].space, put[i].index);  // behind the old record
         t->slots[to] = IdxSlot{idx_tag(put[i].space, put[i].index), idx_pack_a(put[i]), idx_pack_b(put[i]), 0};
         t->live++;
         t->used++;
-        (*fresh)[to] = true;
-        if (had) bury(s);
+        fresh->emplace_back(to, true);
+        if (had) bury(s, tc);
+        tc->fresh = (int32_t)fresh->size() - 1;
     }
+    std::sort(fresh->begin(), fresh->end());  // the device ops go out in slot order
 }
 
-// The update through a rebuild of the host copy: the live records re-inserted, no tombstones.
-void idx_apply_rebuilt(neb_index_table* t, const neb_index_key* del, uint32_t ndel, const neb_index_entry* put,
-                       uint32_t nput) {
-    std::map<uint64_t, std::pair<uint64_t, uint64_t>> recs;
+// The live records after the update, in tag order: what a rebuild re-inserts.
+IdxRecs idx_records_after(const neb_index_table* t, const neb_index_key* del, uint32_t ndel, const neb_index_entry* put,
+                          uint32_t nput) {
+    IdxRecs recs;
     for (const IdxSlot& s : t->slots)
         if (s.tag != kIdxEmpty && s.tag != kIdxTomb) recs[s.tag] = {s.a, s.b};
     for (uint32_t i = 0; i < ndel; i++) recs.erase(idx_tag(del[i].space, del[i].index));
     for (uint32_t i = 0; i < nput; i++) recs[idx_tag(put[i].space, put[i].index)] = {idx_pack_a(put[i]), idx_pack_b(put[i])};
+    return recs;
+}
+
+// The update through a rebuild of the host copy: recs re-inserted, no tombstones. Allocates nothing.
+void idx_apply_rebuilt(neb_index_table* t, const IdxRecs& recs) {
     std::fill(t->slots.begin(), t->slots.end(), IdxSlot{});
     for (const auto& r : recs) {
         const uint32_t space = (uint32_t)(r.first >> 32) & 1u, index = (uint32_t)r.first;
@@ -154,108 +127,12 @@ void idx_apply_rebuilt(neb_index_table* t, const neb_index_key* del, uint32_t nd
 }
 
 #if defined(__HIPCC__)
-#define IDX_HIP(x)                               \
-    do {                                         \
-        if ((x) != hipSuccess) return NEB_ERR_HIP; \
-    } while (0)
-
-// Record that stream s has work on image k in flight (dmu held).
-int idx_note_use(const neb_index_table* t, int k, hipStream_t s) {
-    for (IdxUse& u : t->uses[k])
-        if (u.s == s) {
-            IDX_HIP(hipEventRecord(u.ev, s));
-            return NEB_OK;
-        }
-    Event ev;
-    IDX_HIP(ev.create(hipEventDisableTiming));
-    t->uses[k].push_back(IdxUse{s, std::move(ev)});
-    IDX_HIP(hipEventRecord(t->uses[k].back().ev, s));
-    return NEB_OK;
-}
-
-// ops to the active image in launches of at most kIdxStageOps, through the two staging buffers.
-int idx_scatter_ops(neb_index_table* t, const std::vector<IdxOp>& ops, hipStream_t s) {
-    for (size_t at = 0; at < ops.size(); at += kIdxStageOps) {
-        const uint32_t cnt = (uint32_t)std::min<size_t>(kIdxStageOps, ops.size() - at);
-        const int k = t->stage_next;
-        t->stage_next ^= 1;
-        if (t->stage_busy[k]) IDX_HIP(hipEventSynchronize(t->stage_ev[k]));  // its last launch has read it
-        std::memcpy(t->stage[k], ops.data() + at, (size_t)cnt * sizeof(IdxOp));
-        IDX_HIP(neb_idx_scatter(t->image[t->active], t->stage[k], cnt, s));
-        IDX_HIP(hipEventRecord(t->stage_ev[k], s));
-        t->stage_busy[k] = true;
-    }
-    return NEB_OK;
-}
-
-// The host copy's changes to the active image on s (mu held exclusively).
-int idx_push_update(neb_index_table* t, const std::map<uint32_t, bool>& fresh, const std::vector<uint32_t>& dead,
-                    hipStream_t s) {
-    std::vector<IdxOp> first, second;
-    first.reserve(fresh.size());
-    for (const auto& f : fresh) {
-        const IdxSlot& sl = t->slots[f.first];
-        first.push_back(f.second ? IdxOp{f.first, sl.tag, sl.a, sl.b} : IdxOp{f.first, kIdxTomb, 0, 0});
-    }
-    second.reserve(dead.size());
-    for (uint32_t d : dead) second.push_back(IdxOp{d, kIdxTomb, 0, 0});
-    if (first.empty() && second.empty()) return NEB_OK;
-    std::lock_guard<std::mutex> g(t->dmu);
-    // updates take effect in the order of the calls, whatever their streams
-    if (t->update_pending && t->update_stream != s) IDX_HIP(hipStreamWaitEvent(s, t->update_ev, 0));
-    int rc = idx_scatter_ops(t, first, s);  // new records first: a replaced key is never absent
-    if (rc == NEB_OK) rc = idx_scatter_ops(t, second, s);
-    if (rc != NEB_OK) return rc;
-    IDX_HIP(hipEventRecord(t->update_ev, s));
-    t->update_stream = s;
-    t->update_pending = true;
-    return idx_note_use(t, t->active, s);
-}
-
-// The rebuilt host copy into the spare image, then the switch (mu held exclusively). Blocks.
-int idx_push_rebuild(neb_index_table* t, hipStream_t s) {
-    int spare;
-    std::vector<hipEvent_t> waits;
-    {
-        std::lock_guard<std::mutex> g(t->dmu);
-        spare = t->active ^ 1;
-        for (const IdxUse& u : t->uses[spare]) waits.push_back(u.ev);  // nothing new can start on the spare image
-    }
-    for (hipEvent_t ev : waits) IDX_HIP(hipEventSynchronize(ev));
-    const size_t bytes = t->slots.size() * sizeof(IdxSlot);
-    std::memcpy(t->upload, t->slots.data(), bytes);
-    IDX_HIP(hipMemcpyAsync(t->image[spare], t->upload, bytes, hipMemcpyHostToDevice, s));
-    IDX_HIP(hipStreamSynchronize(s));  // complete before any stream can be pointed at it
-    std::lock_guard<std::mutex> g(t->dmu);
-    t->active = spare;
-    t->update_pending = false;  // later updates go to this image, which nothing else writes
-    return NEB_OK;
-}
-
-// Waits for the device work on the table, then deletes it: its members release themselves
-// (hip_owned.hpp), with the table's device current.
+// Waits for the device work on the table, then deletes it: its members release themselves, with
+// the table's device current.
 void idx_delete_device(neb_index_table* t) {
     DeviceGuard dg(t->device);
-    for (int k = 0; k < 2; k++) {
-        for (IdxUse& u : t->uses[k]) (void)hipEventSynchronize(u.ev);
-        if (t->stage_ev[k]) (void)hipEventSynchronize(t->stage_ev[k]);
-    }
-    if (t->update_ev) (void)hipEventSynchronize(t->update_ev);
+    t->dev.drain();
     delete t;
-}
-
-int idx_init_device(neb_index_table* t) {
-    const size_t bytes = t->slots.size() * sizeof(IdxSlot);
-    for (int k = 0; k < 2; k++) {
-        IDX_HIP(t->image[k].reserve(bytes));
-        IDX_HIP(hipMemset(t->image[k], 0, bytes));
-        IDX_HIP(t->stage[k].reserve(kIdxStageOps * sizeof(IdxOp)));
-        IDX_HIP(t->stage_ev[k].create(hipEventDisableTiming));
-    }
-    IDX_HIP(t->upload.reserve(bytes));
-    IDX_HIP(t->update_ev.create(hipEventDisableTiming));
-    IDX_HIP(hipDeviceSynchronize());  // the images are zero before any stream reads them
-    return NEB_OK;
 }
 #endif
 
@@ -276,7 +153,7 @@ extern "C" NEB_API int neb_index_table_create(neb_engine* e, uint32_t capacity, 
     if (e) {
         t->device = neb_engine_device_of(e);
         DeviceGuard dg(t->device);
-        const int rc = idx_init_device(t);
+        const int rc = t->dev.init(t->slots.size());
         if (rc != NEB_OK) {
             idx_delete_device(t);
             return rc;
@@ -300,26 +177,65 @@ extern "C" NEB_API int neb_index_table_destroy(neb_index_table* t) {
 }
 
 extern "C" NEB_API int neb_index_table_update(neb_index_table* t, const neb_index_key* del, uint32_t ndel,
-                                              const neb_index_entry* put, uint32_t nput, void* stream) {
+                                              const neb_index_entry* put, uint32_t nput, void* stream) try {
     if (!t) return NEB_ERR_INVALID;
     const int rc = idx_validate(del, ndel, put, nput);
     if (rc != NEB_OK) return rc;
     std::unique_lock<std::shared_mutex> g(t->mu);
-    if (idx_live_after(t, del, ndel, put, nput) > t->capacity) return NEB_ERR_NO_KEY_SLOT;
+    // Everything that allocates comes first, so that an allocation failure applies nothing.
+    // Entries live after the call: the deletions, then the puts, over the keys the call names.
+    std::unordered_map<uint64_t, IdxTouch> now;
+    int64_t live = (int64_t)t->live;
+    auto touch = [&](uint32_t space, uint32_t index, bool to) {
+        const uint64_t tag = idx_tag(space, index);
+        auto it = now.find(tag);
+        if (it == now.end()) {
+            uint32_t s, p;
+            it = now.emplace(tag, IdxTouch{idx_find_host(t, space, index, &s, &p), -1}).first;
+        }
+        live += (int)to - (int)it->second.live;
+        it->second.live = to;
+    };
+    for (uint32_t i = 0; i < ndel; i++) touch(del[i].space, del[i].index, false);
+    for (uint32_t i = 0; i < nput; i++) touch(put[i].space, put[i].index, true);
+    if (live > (int64_t)t->capacity) return NEB_ERR_NO_KEY_SLOT;
     // every put takes a slot; past 3/4 of the slots in use the table is rebuilt without its tombstones
     const bool rebuild = (uint64_t)t->used + nput > (uint64_t)(t->mask + 1u) / 4u * 3u;
-    std::map<uint32_t, bool> fresh;
+    IdxRecs recs;
+    std::vector<std::pair<uint32_t, bool>> fresh;
     std::vector<uint32_t> dead;
-    if (rebuild) idx_apply_rebuilt(t, del, ndel, put, nput);
-    else idx_apply(t, del, ndel, put, nput, &fresh, &dead);
+    if (rebuild) {
+        recs = idx_records_after(t, del, ndel, put, nput);
+    } else {
+        fresh.reserve(nput);
+        dead.reserve((size_t)ndel + nput);
+    }
+#if defined(__HIPCC__)
+    std::vector<IdxOp> first, second;
+    if (!rebuild && t->device >= 0) {
+        first.reserve(nput);
+        second.reserve((size_t)ndel + nput);
+    }
+#endif
+    // From here on nothing allocates on the host.
+    if (rebuild) idx_apply_rebuilt(t, recs);
+    else idx_apply(t, del, ndel, put, nput, &now, &fresh, &dead);
 #if defined(__HIPCC__)
     if (t->device >= 0) {
         DeviceGuard dg(t->device);
-        return rebuild ? idx_push_rebuild(t, (hipStream_t)stream) : idx_push_update(t, fresh, dead, (hipStream_t)stream);
+        if (rebuild) return t->dev.rebuild(t->slots.data(), (hipStream_t)stream);
+        for (const auto& f : fresh) {
+            const IdxSlot& sl = t->slots[f.first];
+            first.push_back(f.second ? IdxOp{f.first, sl.tag, sl.a, sl.b} : IdxOp{f.first, kIdxTomb, 0, 0});
+        }
+        for (uint32_t d : dead) second.push_back(IdxOp{d, kIdxTomb, 0, 0});
+        return t->dev.update(first, second, (hipStream_t)stream, neb_idx_scatter);
     }
 #endif
     (void)stream;
     return NEB_OK;
+} catch (const std::bad_alloc&) {
+    return NEB_ERR_INVALID;
 }
 
 extern "C" NEB_API int neb_index_table_set_own_networks(neb_index_table* t, const neb_cidr* nets, uint32_t n,
@@ -327,7 +243,7 @@ extern "C" NEB_API int neb_index_table_set_own_networks(neb_index_table* t, cons
     (void)stream;
     if (!t || n > NEB_INDEX_MAX_NETWORKS || (n && !nets)) return NEB_ERR_INVALID;
     for (uint32_t k = 0; k < n; k++)
-        if (!idx_cidr_ok(nets[k])) return NEB_ERR_INVALID;
+        if (!cidr_ok(nets[k])) return NEB_ERR_INVALID;
     IdxNets v;
     idx_nets_set(&v, nets, n);
     std::unique_lock<std::shared_mutex> g(t->mu);
@@ -372,7 +288,7 @@ extern "C" NEB_API int neb_rx_resolve_batch_host(const neb_index_table* t, neb_r
             std::memcpy(w1, h + 4, 4);
         };
         auto look = [&](uint32_t space, uint32_t index, bool want_route, IdxRec* r) {
-            return idx_lookup(t->slots.data(), t->mask, space, index, IdxHostLoad{}, want_route, r);
+            return idx_lookup(t->slots.data(), t->mask, space, index, HostLoad{}, want_route, r);
         };
         uint32_t key;
         neb_relay_route r;
@@ -399,10 +315,9 @@ extern "C" NEB_API int neb_rx_resolve_batch(neb_engine* e, const neb_index_table
         nets = t->nets;
     }
     DeviceGuard dg(t->device);
-    std::lock_guard<std::mutex> g(t->dmu);
-    const int k = t->active;
-    IDX_HIP(neb_idx_resolve(t->image[k], t->mask, &nets, d_pk, d_src, n, d_arena, d_route, d_via, (hipStream_t)stream));
-    return idx_note_use(t, k, (hipStream_t)stream);  // a rebuild into this image waits for it
+    return t->dev.read((hipStream_t)stream, [&](int, const IdxSlot* image) {
+        return neb_idx_resolve(image, t->mask, &nets, d_pk, d_src, n, d_arena, d_route, d_via, (hipStream_t)stream);
+    });
 #else
     (void)e, (void)t, (void)d_pk, (void)d_src, (void)n, (void)d_arena, (void)d_route, (void)d_via, (void)stream;
     return NEB_ERR_NO_DEVICE;

@@ -108,7 +108,8 @@ struct IdxNets {
     uint32_t mask[NEB_INDEX_MAX_NETWORKS][4];
 };
 
-inline bool idx_cidr_ok(const neb_cidr& c) {
+// A prefix the tables take (both; route_core.hpp): a family, and no more bits than it has.
+inline bool cidr_ok(const neb_cidr& c) {
     return (c.family == 4 && c.bits <= 32) || (c.family == 6 && c.bits <= 128);
 }
 inline void idx_nets_set(IdxNets* out, const neb_cidr* nets, uint32_t n) {

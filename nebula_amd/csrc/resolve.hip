@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nebula_aead.h"
+#include "device_common.hpp"
 #include "index_core.hpp"
 #include "resolve.hpp"
 
@@ -33,14 +34,6 @@ struct ResolveArgs {
     neb_relay_route* route;
     neb_rx_via* via;
     IdxNets nets;  // in the kernel arguments: scanned through the scalar cache, wave-uniformly
-};
-
-struct IdxLoadAgent {
-    __device__ __forceinline__ uint64_t operator()(const uint64_t* p) const {
-        const uint64_t v = __hip_atomic_load(const_cast<uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the loads in program order
-        return v;
-    }
 };
 
 __global__ __launch_bounds__(256) void idx_resolve_kernel(ResolveArgs a) {
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(256) void idx_resolve_kernel(ResolveArgs a) {
         }
     };
     auto look = [&](uint32_t space, uint32_t index, bool want_route, IdxRec* r) {
-        return idx_lookup(a.image, a.mask, space, index, IdxLoadAgent{}, want_route, r);
+        return idx_lookup(a.image, a.mask, space, index, LoadAgent{}, want_route, r);
     };
     uint32_t key;
     neb_relay_route route;

@@ -19,9 +19,7 @@ struct IdxOp {
 }  // namespace neb
 
 // ops[0..n) applied to `image` on s, one thread each (every op names another slot). A record is
-// written and released before its tag is published. The caller orders the launches: a call's new
-// records (and the slots it filled and emptied again) first, the tombstones of records that were
-// live before in a second launch.
+// written and released before its tag is published. The order of the launches is table_mirror.hpp's.
 extern "C" hipError_t neb_idx_scatter(neb::IdxSlot* image, const neb::IdxOp* ops, uint32_t n, hipStream_t s);
 // neb_rx_resolve_batch's kernel on s over `image` (mask + 1 slots). nets travels by value.
 extern "C" hipError_t neb_idx_resolve(const neb::IdxSlot* image, uint32_t mask, const neb::IdxNets* nets,

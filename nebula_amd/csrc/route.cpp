@@ -1,11 +1,10 @@
 // route.cpp — neb_tx_table_* and neb_tx_resolve_batch[_host]: the table of the TX-side lookups (VPN
-// address -> tunnel, unsafe routes, ECMP gateways; rules: route_core.hpp). The index table's design
-// (index.cpp) with a wider key: the host copy is authoritative, every update is applied to it first
-// under the table's lock, and neb_tx_resolve_batch_host reads it. A table made with an engine also
-// keeps two images in device memory, each the slots and the gateway array: host updates go to the
-// active one through a scatter kernel on the caller's stream (route.hip); a compaction and every
-// neb_tx_table_set_routes write the spare one and switch. Compiled without HIP (g++:
-// tests/sanitize_route) only the host-only table exists.
+// address -> tunnel, unsafe routes, ECMP gateways; rules: route_core.hpp). The host copy is
+// authoritative: every update is applied to it first under the table's lock, and
+// neb_tx_resolve_batch_host reads it. A table made with an engine also keeps a device copy
+// (table_mirror.hpp), written by route.hip's scatter; each image has its gateway array and set of
+// prefix lengths, so a compaction and every neb_tx_table_set_routes go through a rebuild. Compiled
+// without HIP (g++: tests/sanitize_route) only the host-only table exists.
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -18,6 +17,7 @@
 #include <vector>
 
 #include "route_core.hpp"
+#include "table_mirror.hpp"
 
 #if defined(__HIPCC__)
 #include "engine_internal.hpp"
@@ -30,19 +30,6 @@ using namespace neb;
 namespace {
 
 constexpr uint32_t kTxMaxCapacity = 1u << 20;  // per kind: a host copy of at most 256 MiB
-#if defined(__HIPCC__)
-constexpr uint32_t kTxStageOps = 4096;  // ops per scatter launch (two pinned staging buffers)
-
-struct TxUse {  // the last work a stream has enqueued on an image
-    hipStream_t s;
-    neb::Event ev;
-};
-#endif
-
-struct TxHostLoad {
-    uint64_t operator()(const uint64_t* p) const { return *p; }
-};
-
 using TxKey = std::tuple<uint32_t, uint64_t, uint64_t>;  // family, hi, lo
 struct TxTouch {  // one address an update names
     bool live;      // is it live now
@@ -75,23 +62,12 @@ struct neb_tx_table {
     TxOwn own{};
 #if defined(__HIPCC__)
     int device = -1;  // -1: host-only
-    // dmu: which image is active, the events and `down` (taken inside mu by writers, alone by resolves)
-    mutable std::mutex dmu;
-    DevBuf<TxSlot> image[2];
+    // the device copy; its lock (also `down`'s) is taken inside mu by writers, alone by the resolve
+    TableMirror<HipWsApi, TxSlot, TxOp> dev;
     DevBuf<TxGw> dgw[2];
     TxLens dlens[2] = {};  // switch with the image
-    TxOwn down{};          // own, for the device resolve: it takes dmu only, never mu
-    int active = 0;
-    mutable std::vector<TxUse> uses[2];
-    PinnedBuf<TxOp> stage[2];
-    Event stage_ev[2];
-    bool stage_busy[2] = {false, false};
-    int stage_next = 0;
-    PinnedBuf<TxSlot> upload;  // a rebuilt image on its way to the device
+    TxOwn down{};          // own, for the device resolve: it never takes mu
     PinnedBuf<TxGw> upload_gw;
-    Event update_ev;
-    hipStream_t update_stream = nullptr;
-    bool update_pending = false;
 #endif
 };
 
@@ -99,7 +75,7 @@ namespace {
 
 inline bool tx_find_host(const neb_tx_table* t, uint32_t kind, uint32_t family, uint32_t bits, const TxAddr& a,
                          uint32_t* slot, uint32_t* probes) {
-    return tx_find(t->slots.data(), t->mask, kind, family, bits, a, TxHostLoad{}, slot, probes);
+    return tx_find(t->slots.data(), t->mask, kind, family, bits, a, HostLoad{}, slot, probes);
 }
 
 // Puts a record into the first EMPTY slot of its chain (the table always has one).
@@ -149,118 +125,32 @@ void tx_apply(neb_tx_table* t, const neb_tx_addr* del, uint32_t ndel, const neb_
 }
 
 #if defined(__HIPCC__)
-#define TX_HIP(x)                                \
-    do {                                         \
-        if ((x) != hipSuccess) return NEB_ERR_HIP; \
-    } while (0)
-
-// Record that stream s has work on image k in flight (dmu held).
-int tx_note_use(const neb_tx_table* t, int k, hipStream_t s) {
-    for (TxUse& u : t->uses[k])
-        if (u.s == s) {
-            TX_HIP(hipEventRecord(u.ev, s));
-            return NEB_OK;
-        }
-    Event ev;
-    TX_HIP(ev.create(hipEventDisableTiming));
-    try {
-        t->uses[k].push_back(TxUse{s, std::move(ev)});
-    } catch (const std::bad_alloc&) {
-        return NEB_ERR_INVALID;
-    }
-    TX_HIP(hipEventRecord(t->uses[k].back().ev, s));
-    return NEB_OK;
-}
-
-// ops to the active image in launches of at most kTxStageOps, through the two staging buffers.
-int tx_scatter_ops(neb_tx_table* t, const std::vector<TxOp>& ops, hipStream_t s) {
-    for (size_t at = 0; at < ops.size(); at += kTxStageOps) {
-        const uint32_t cnt = (uint32_t)std::min<size_t>(kTxStageOps, ops.size() - at);
-        const int k = t->stage_next;
-        t->stage_next ^= 1;
-        if (t->stage_busy[k]) TX_HIP(hipEventSynchronize(t->stage_ev[k]));  // its last launch has read it
-        std::memcpy(t->stage[k], ops.data() + at, (size_t)cnt * sizeof(TxOp));
-        TX_HIP(neb_txt_scatter(t->image[t->active], t->mask, t->stage[k], cnt, s));
-        TX_HIP(hipEventRecord(t->stage_ev[k], s));
-        t->stage_busy[k] = true;
-    }
-    return NEB_OK;
-}
-
-// The host copy's changes to the active image on s (mu held exclusively).
-int tx_push_update(neb_tx_table* t, const std::vector<std::pair<uint32_t, bool>>& fresh, const std::vector<uint32_t>& dead,
-                   std::vector<TxOp>& first, std::vector<TxOp>& second, hipStream_t s) {  // first, second: reserved
-    for (const auto& f : fresh) {
-        const TxSlot& sl = t->slots[f.first];
-        first.push_back(f.second ? TxOp{f.first, sl.tag, sl.addr_lo, sl.addr_hi, sl.value} : TxOp{f.first, kTxTomb, 0, 0, 0});
-    }
-    for (uint32_t d : dead) second.push_back(TxOp{d, kTxTomb, 0, 0, 0});
-    if (first.empty() && second.empty()) return NEB_OK;
-    std::lock_guard<std::mutex> g(t->dmu);
-    // updates take effect in the order of the calls, whatever their streams
-    if (t->update_pending && t->update_stream != s) TX_HIP(hipStreamWaitEvent(s, t->update_ev, 0));
-    int rc = tx_scatter_ops(t, first, s);  // new records first: a replaced address is never absent
-    if (rc == NEB_OK) rc = tx_scatter_ops(t, second, s);
-    if (rc != NEB_OK) return rc;
-    TX_HIP(hipEventRecord(t->update_ev, s));
-    t->update_stream = s;
-    t->update_pending = true;
-    return tx_note_use(t, t->active, s);
-}
-
 // The rebuilt host copy and the gateways into the spare image, then the switch of image, gateways
 // and prefix lengths together (mu held exclusively). Blocks.
 int tx_push_rebuild(neb_tx_table* t, hipStream_t s) {
-    int spare;
-    std::vector<hipEvent_t> waits;
-    {
-        std::lock_guard<std::mutex> g(t->dmu);
-        spare = t->active ^ 1;
-        for (const TxUse& u : t->uses[spare]) waits.push_back(u.ev);  // nothing new can start on the spare image
-    }
-    for (hipEvent_t ev : waits) TX_HIP(hipEventSynchronize(ev));
-    const size_t bytes = t->slots.size() * sizeof(TxSlot), gbytes = t->gws.size() * sizeof(TxGw);
-    std::memcpy(t->upload, t->slots.data(), bytes);
-    TX_HIP(hipMemcpyAsync(t->image[spare], t->upload, bytes, hipMemcpyHostToDevice, s));
-    if (gbytes) {
+    auto gateways = [&](int spare, hipStream_t st) {
+        const size_t gbytes = t->gws.size() * sizeof(TxGw);
+        if (!gbytes) return hipSuccess;
         std::memcpy(t->upload_gw, t->gws.data(), gbytes);
-        TX_HIP(hipMemcpyAsync(t->dgw[spare], t->upload_gw, gbytes, hipMemcpyHostToDevice, s));
-    }
-    TX_HIP(hipStreamSynchronize(s));  // complete before any stream can be pointed at it
-    std::lock_guard<std::mutex> g(t->dmu);
-    t->active = spare;
-    t->dlens[spare] = t->lens;
-    t->update_pending = false;  // later updates go to this image, which nothing else writes
-    return NEB_OK;
+        return HipWsApi::copy_h2d(t->dgw[spare], t->upload_gw, gbytes, st);
+    };
+    return t->dev.rebuild(t->slots.data(), s, gateways, [&](int spare) { t->dlens[spare] = t->lens; });
 }
 
-// Waits for the device work on the table, then deletes it: its members release themselves
-// (hip_owned.hpp), with the table's device current.
+// Waits for the device work on the table, then deletes it: its members release themselves, with
+// the table's device current.
 void tx_delete_device(neb_tx_table* t) {
     DeviceGuard dg(t->device);
-    for (int k = 0; k < 2; k++) {
-        for (TxUse& u : t->uses[k]) (void)hipEventSynchronize(u.ev);
-        if (t->stage_ev[k]) (void)hipEventSynchronize(t->stage_ev[k]);
-    }
-    if (t->update_ev) (void)hipEventSynchronize(t->update_ev);
+    t->dev.drain();
     delete t;
 }
 
 int tx_init_device(neb_tx_table* t) {
-    const size_t bytes = t->slots.size() * sizeof(TxSlot), gbytes = std::max<size_t>(1, t->gw_cap) * sizeof(TxGw);
-    for (int k = 0; k < 2; k++) {
-        TX_HIP(t->image[k].reserve(bytes));
-        TX_HIP(hipMemset(t->image[k], 0, bytes));
-        TX_HIP(t->dgw[k].reserve(gbytes));
-        TX_HIP(hipMemset(t->dgw[k], 0, gbytes));
-        TX_HIP(t->stage[k].reserve(kTxStageOps * sizeof(TxOp)));
-        TX_HIP(t->stage_ev[k].create(hipEventDisableTiming));
-    }
-    TX_HIP(t->upload.reserve(bytes));
-    TX_HIP(t->upload_gw.reserve(gbytes));
-    TX_HIP(t->update_ev.create(hipEventDisableTiming));
-    TX_HIP(hipDeviceSynchronize());  // the images are zero before any stream reads them
-    return NEB_OK;
+    const size_t gbytes = std::max<size_t>(1, t->gw_cap) * sizeof(TxGw);
+    for (int k = 0; k < 2; k++)
+        if (t->dgw[k].reserve(gbytes) != hipSuccess || HipWsApi::memset(t->dgw[k], 0, gbytes) != hipSuccess) return NEB_ERR_HIP;
+    if (t->upload_gw.reserve(gbytes) != hipSuccess) return NEB_ERR_HIP;
+    return t->dev.init(t->slots.size());  // (synchronises the device: the gateway arrays are zero too)
 }
 #endif
 
@@ -366,8 +256,15 @@ extern "C" NEB_API int neb_tx_table_update_hosts(neb_tx_table* t, const neb_tx_a
 #if defined(__HIPCC__)
     if (t->device >= 0) {
         DeviceGuard dg(t->device);
-        return rebuild ? tx_push_rebuild(t, (hipStream_t)stream)
-                       : tx_push_update(t, fresh, dead, first, second, (hipStream_t)stream);
+        if (rebuild) return tx_push_rebuild(t, (hipStream_t)stream);
+        for (const auto& f : fresh) {
+            const TxSlot& sl = t->slots[f.first];
+            first.push_back(f.second ? TxOp{f.first, sl.tag, sl.addr_lo, sl.addr_hi, sl.value} : TxOp{f.first, kTxTomb, 0, 0, 0});
+        }
+        for (uint32_t d : dead) second.push_back(TxOp{d, kTxTomb, 0, 0, 0});
+        return t->dev.update(first, second, (hipStream_t)stream, [&](TxSlot* image, const TxOp* ops, uint32_t cnt, hipStream_t s) {
+            return neb_txt_scatter(image, t->mask, ops, cnt, s);
+        });
     }
 #endif
     (void)stream;
@@ -385,7 +282,7 @@ extern "C" NEB_API int neb_tx_table_set_routes(neb_tx_table* t, const neb_route*
     std::set<std::tuple<uint32_t, uint32_t, uint64_t, uint64_t>> seen;
     for (uint32_t i = 0; i < nroutes; i++) {
         const neb_route& r = routes[i];
-        if (!tx_cidr_ok(r.prefix) || r.ngateways == 0 || r.ngateways > NEB_ROUTE_MAX_GATEWAYS) return NEB_ERR_INVALID;
+        if (!cidr_ok(r.prefix) || r.ngateways == 0 || r.ngateways > NEB_ROUTE_MAX_GATEWAYS) return NEB_ERR_INVALID;
         uint64_t total = 0, upto = 0;
         for (uint32_t k = 0; k < r.ngateways; k++) {
             if (!tx_family_ok(r.gateways[k].addr.family)) return NEB_ERR_INVALID;
@@ -426,13 +323,13 @@ extern "C" NEB_API int neb_tx_table_set_own(neb_tx_table* t, const neb_cidr* net
     if (!t || n > NEB_INDEX_MAX_NETWORKS || (n && !nets) || (flags & ~(NEB_TX_DROP_LOCAL_BROADCAST | NEB_TX_DROP_MULTICAST)))
         return NEB_ERR_INVALID;
     for (uint32_t k = 0; k < n; k++)
-        if (!tx_cidr_ok(nets[k])) return NEB_ERR_INVALID;
+        if (!cidr_ok(nets[k])) return NEB_ERR_INVALID;
     TxOwn v;
     tx_own_set(&v, nets, n, flags);
     std::unique_lock<std::shared_mutex> g(t->mu);
     t->own = v;
 #if defined(__HIPCC__)
-    std::lock_guard<std::mutex> dg(t->dmu);
+    std::lock_guard<std::mutex> dg(t->dev.lock());
     t->down = v;
 #endif
     return NEB_OK;
@@ -448,7 +345,7 @@ extern "C" NEB_API int neb_tx_table_count(const neb_tx_table* t, uint32_t* hosts
 
 extern "C" NEB_API int neb_tx_table_probe(const neb_tx_table* t, uint32_t kind, const neb_cidr* key, uint32_t out[3]) {
     if (!t || !key || !out || kind > NEB_TX_KIND_ROUTE || !tx_family_ok(key->family)) return NEB_ERR_INVALID;
-    if (kind == NEB_TX_KIND_ROUTE && !tx_cidr_ok(*key)) return NEB_ERR_INVALID;
+    if (kind == NEB_TX_KIND_ROUTE && !cidr_ok(*key)) return NEB_ERR_INVALID;
     const uint32_t bits = kind == NEB_TX_KIND_ROUTE ? key->bits : 0;
     TxAddr a = tx_addr_from_bytes(key->addr, key->family);
     if (kind == NEB_TX_KIND_ROUTE) {
@@ -470,7 +367,7 @@ extern "C" NEB_API int neb_tx_resolve_batch_host(const neb_tx_table* t, neb_tx_p
         const uint8_t* d = in + pk[i].in_off;
         auto byte = [&](uint32_t k) -> uint32_t { return d[k]; };
         auto look = [&](uint32_t kind, uint32_t family, uint32_t bits, const TxAddr& a, uint64_t* v) {
-            return tx_lookup(t->slots.data(), t->mask, kind, family, bits, a, TxHostLoad{}, v);
+            return tx_lookup(t->slots.data(), t->mask, kind, family, bits, a, HostLoad{}, v);
         };
         auto gw = [&](uint32_t k) { return t->gws[k]; };
         TxResult r;
@@ -489,13 +386,11 @@ extern "C" NEB_API int neb_tx_resolve_batch(neb_engine* e, const neb_tx_table* t
         (reinterpret_cast<uintptr_t>(d_fw) & 15u))
         return NEB_ERR_INVALID;
     if (n == 0) return NEB_OK;
-    // dmu only: a rebuild or route replacement in progress holds mu and does not stall this call
+    // the mirror's lock only: a rebuild or route replacement in progress holds mu and does not stall this call
     DeviceGuard dg(t->device);
-    std::lock_guard<std::mutex> g(t->dmu);
-    const int k = t->active;
-    TX_HIP(neb_txt_resolve(t->image[k], t->mask, t->dgw[k], &t->dlens[k], &t->down, d_pk, n, d_in, d_fw, d_status,
-                           (hipStream_t)stream));
-    return tx_note_use(t, k, (hipStream_t)stream);  // a rebuild into this image waits for it
+    return t->dev.read((hipStream_t)stream, [&](int k, const TxSlot* image) {
+        return neb_txt_resolve(image, t->mask, t->dgw[k], &t->dlens[k], &t->down, d_pk, n, d_in, d_fw, d_status, (hipStream_t)stream);
+    });
 #else
     (void)e, (void)t, (void)d_pk, (void)n, (void)d_in, (void)d_fw, (void)d_status, (void)stream;
     return NEB_ERR_NO_DEVICE;

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nebula_aead.h"
+#include "device_common.hpp"
 #include "route.hpp"
 #include "route_core.hpp"
 
@@ -34,14 +35,6 @@ struct TxResolveArgs {
     uint32_t n;
     TxLens lens;  // in the kernel arguments: scanned through the scalar cache, wave-uniformly
     TxOwn own;
-};
-
-struct TxLoadAgent {
-    __device__ __forceinline__ uint64_t operator()(const uint64_t* p) const {
-        const uint64_t v = __hip_atomic_load(const_cast<uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the loads in program order
-        return v;
-    }
 };
 
 __global__ __launch_bounds__(256) void tx_resolve_kernel(TxResolveArgs a) {
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(256) void tx_resolve_kernel(TxResolveArgs a) {
         return h[k];
     };
     auto look = [&](uint32_t kind, uint32_t family, uint32_t bits, const TxAddr& addr, uint64_t* v) {
-        return tx_lookup(a.image, a.mask, kind, family, bits, addr, TxLoadAgent{}, v);
+        return tx_lookup(a.image, a.mask, kind, family, bits, addr, LoadAgent{}, v);
     };
     auto gw = [&](uint32_t k) { return a.gws[k]; };
     TxResult r;

@@ -19,8 +19,7 @@ struct TxOp {
 }  // namespace neb
 
 // ops[0..n) applied to `image` (mask + 1 slots) on s, one thread each (every op names another
-// slot). A record is written and released before its tag is published. The caller orders the
-// launches as for neb_idx_scatter (resolve.hpp).
+// slot). A record is written and released before its tag is published.
 extern "C" hipError_t neb_txt_scatter(neb::TxSlot* image, uint32_t mask, const neb::TxOp* ops, uint32_t n, hipStream_t s);
 // neb_tx_resolve_batch's kernel on s over `image` (mask + 1 slots) and its gateway array. lens and
 // own travel by value.

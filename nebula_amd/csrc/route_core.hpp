@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/nebula_aead.h"
+#include "index_core.hpp"  // cidr_ok
 
 #if defined(__HIPCC__)
 #define NEB_RT_HD __host__ __device__ inline __attribute__((always_inline))
@@ -85,9 +86,6 @@ struct TxOwn {
     uint64_t bcast[NEB_INDEX_MAX_NETWORKS];  // family 4: network | ~mask, as TxAddr.hi
 };
 
-inline bool tx_cidr_ok(const neb_cidr& c) {
-    return (c.family == 4 && c.bits <= 32) || (c.family == 6 && c.bits <= 128);
-}
 inline void tx_own_set(TxOwn* o, const neb_cidr* nets, uint32_t n, uint32_t flags) {
     *o = TxOwn{};
     o->n = n;

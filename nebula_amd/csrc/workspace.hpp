@@ -5,7 +5,10 @@
 // s, end(s). Host-only logic over a device policy, like queue_core.hpp: the engine binds it to HIP
 // (HipWsApi below), tests/sanitize/workspace_test.cpp to a fake that logs the calls. Api has Stream,
 // Event, Error, kOk, event_create / _sync / _record / _destroy, stream_wait, stream_id (0 = the
-// runtime gives none), mem_alloc and mem_free; hip_owned.hpp's buffers add host_alloc and host_free.
+// runtime gives none), mem_alloc and mem_free; hip_owned.hpp's buffers add host_alloc and host_free;
+// table_mirror.hpp's images add memset, copy_h2d (asynchronous, from pinned memory), stream_sync,
+// device_sync, kPinned (the host_alloc flags of its staging) and event_create_host: an event the
+// host waits for, with timing disabled and nothing else.
 #pragma once
 
 #include <cstddef>
@@ -122,6 +125,14 @@ struct HipWsApi {
     static void mem_free(uint8_t* p) { (void)hipFree(p); }
     static hipError_t host_alloc(uint8_t** p, size_t bytes, unsigned flags) { return hipHostMalloc((void**)p, bytes, flags); }
     static void host_free(uint8_t* p) { (void)hipHostFree(p); }
+    static constexpr unsigned kPinned = hipHostMallocDefault;
+    static hipError_t event_create_host(hipEvent_t* ev) { return hipEventCreateWithFlags(ev, hipEventDisableTiming); }
+    static hipError_t memset(void* p, int v, size_t bytes) { return hipMemset(p, v, bytes); }
+    static hipError_t copy_h2d(void* dst, const void* src, size_t bytes, hipStream_t s) {
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    }
+    static hipError_t stream_sync(hipStream_t s) { return hipStreamSynchronize(s); }
+    static hipError_t device_sync() { return hipDeviceSynchronize(); }
 };
 template <int N = 1>
 using HipWorkspace = DevWorkspace<HipWsApi, N>;

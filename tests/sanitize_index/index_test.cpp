@@ -2,7 +2,9 @@
 // sanitizers: a stand-alone program, no HIP and no GPU.
 //   exact    (the ASan + UBSan build) random updates against a std::map, and the host resolve of
 //            packets that each live in a heap buffer of exactly their length, with exact-size
-//            record arrays: an over-read or a stray write is an ASan report.
+//            record arrays: an over-read or a stray write is an ASan report. Then del + put +
+//            re-put sequences over the same keys, up to and across the rebuild threshold, against
+//            a model that finds its records by linear scan: every key's slot and probe count.
 //   threads  (the TSan build) four threads call neb_index_table_update — puts, replaces and deletes
 //            of their own churn keys, replaces of the shared steady keys with the same record,
 //            through many rebuilds — while two threads run the host resolve: a steady key always
@@ -140,6 +142,105 @@ static void exact() {
     CHECK(neb_index_table_destroy(t) == NEB_OK);
 }
 
+// The table's slot discipline restated with linear scans: a record is found by looking at every
+// slot; a put goes to the first EMPTY slot from the key's home, behind the record it replaces, which
+// is tombstoned afterwards; past 3/4 of the slots in use the live records are re-inserted in tag order.
+struct SlotModel {
+    std::vector<uint64_t> tag;  // 0: EMPTY, 1: TOMBSTONE
+    std::vector<uint32_t> key;  // the record's key_id
+    uint32_t used = 0;
+    explicit SlotModel(uint32_t capacity) : tag(neb::idx_slots_for(capacity), 0), key(tag.size(), 0) {}
+    int scan(uint64_t want) const {
+        for (size_t s = 0; s < tag.size(); s++)
+            if (tag[s] == want) return (int)s;
+        return -1;
+    }
+    void insert(uint64_t t, uint32_t space, uint32_t index, uint32_t key_id) {
+        size_t s = neb::idx_hash(space, index) % tag.size();
+        while (tag[s] != 0) s = (s + 1) % tag.size();
+        tag[s] = t;
+        key[s] = key_id;
+        used++;
+    }
+    bool update(const std::vector<neb_index_key>& del, const std::vector<neb_index_entry>& put) {  // true: it rebuilt
+        if ((uint64_t)used + put.size() > tag.size() / 4 * 3) {
+            std::map<uint64_t, uint32_t> recs;
+            for (size_t s = 0; s < tag.size(); s++)
+                if (tag[s] > 1) recs[tag[s]] = key[s];
+            for (auto& d : del) recs.erase(neb::idx_tag(d.space, d.index));
+            for (auto& p : put) recs[neb::idx_tag(p.space, p.index)] = p.key_id;
+            std::fill(tag.begin(), tag.end(), 0);
+            used = 0;
+            for (auto& r : recs) insert(r.first, (uint32_t)(r.first >> 32) & 1u, (uint32_t)r.first, r.second);
+            return true;
+        }
+        for (auto& d : del) {
+            const int s = scan(neb::idx_tag(d.space, d.index));
+            if (s >= 0) tag[(size_t)s] = 1;
+        }
+        for (auto& p : put) {
+            const int old = scan(neb::idx_tag(p.space, p.index));
+            insert(neb::idx_tag(p.space, p.index), p.space, p.index, p.key_id);
+            if (old >= 0) tag[(size_t)old] = 1;
+        }
+        return false;
+    }
+    // what neb_index_table_probe answers: found, the slot the walk ended at, slots examined
+    void probe(uint32_t space, uint32_t index, uint32_t out[3]) const {
+        const uint64_t want = neb::idx_tag(space, index);
+        size_t s = neb::idx_hash(space, index) % tag.size();
+        uint32_t k = 1;
+        while (tag[s] != want && tag[s] != 0) s = (s + 1) % tag.size(), k++;
+        out[0] = tag[s] == want, out[1] = (uint32_t)s, out[2] = k;
+    }
+};
+
+// del + put + re-put of the same keys in one call, again and again, until live + tombstones + puts
+// is exactly `last` of the 32 slots' threshold of 24: at 24 the call still goes slot by slot, at 25
+// it rebuilds.
+static void exact_slots(uint32_t last) {
+    neb_index_table* t = nullptr;
+    CHECK(neb_index_table_create(nullptr, 8, &t) == NEB_OK);
+    SlotModel m(8);
+    CHECK(m.tag.size() == 32);
+    const uint32_t idx[5] = {7, 39, 0x80000007u, 71, 1000};  // the last is never put
+    uint32_t next_key = 1;
+    auto step = [&](uint32_t nput) {
+        // deletes the first two keys, puts the first again, then others, then the first once more
+        std::vector<neb_index_key> del = {neb_index_key{idx[0], 0}, neb_index_key{idx[1], 1}};
+        std::vector<neb_index_entry> put;
+        for (uint32_t i = 0; i + 1 < nput; i++) put.push_back(entry(i & 1, idx[i % 4], next_key++, 0, NEB_RELAY_NONE, 0));
+        put.push_back(entry(0, idx[0], next_key++, 0, NEB_RELAY_NONE, 0));
+        CHECK(neb_index_table_update(t, del.data(), 2, put.data(), nput, nullptr) == NEB_OK);
+        const bool rebuilt = m.update(del, put);
+        uint32_t live = 0, want_live = 0;
+        for (uint64_t tg : m.tag) want_live += tg > 1;
+        CHECK(neb_index_table_count(t, &live) == NEB_OK && live == want_live);
+        for (uint32_t space = 0; space < 2; space++)
+            for (uint32_t index : idx) {
+                uint32_t got[3], want[3];
+                CHECK(neb_index_table_probe(t, space, index, got) == NEB_OK);
+                m.probe(space, index, want);
+                CHECK(got[0] == want[0] && got[1] == want[1] && got[2] == want[2]);
+                uint8_t h[16];
+                put_header(h, 1, (uint8_t)space, index);
+                neb_rx_packet pk{0, 16, 0};
+                CHECK(neb_rx_resolve_batch_host(t, &pk, nullptr, 1, h, 16, nullptr, nullptr) == NEB_OK);
+                CHECK(pk.key_id == (want[0] ? m.key[want[1]] : NEB_KEYS_MIXED));
+            }
+        return rebuilt;
+    };
+    while (m.used + 6 <= last) CHECK(!step(3));
+    CHECK(m.used == 21);
+    const uint32_t before = m.used;
+    const bool rebuilt = step(last - before);
+    CHECK(rebuilt == (last > 24));
+    if (rebuilt) CHECK(m.used <= 4);  // the live records alone
+    else CHECK(m.used == 24);         // tombstones and all
+    CHECK(step(3) == !rebuilt);       // and the call after it, on the other side
+    CHECK(neb_index_table_destroy(t) == NEB_OK);
+}
+
 static void threads() {
     constexpr uint32_t kSteady = 16, kChurn = 4, kUpdaters = 4, kRounds = 3000;
     neb_index_table* t = nullptr;
@@ -198,7 +299,11 @@ static void threads() {
 
 int main(int argc, char** argv) {
     const bool both = argc < 2;
-    if (both || !std::strcmp(argv[1], "exact")) exact();
+    if (both || !std::strcmp(argv[1], "exact")) {
+        exact();
+        exact_slots(24);
+        exact_slots(25);
+    }
     if (both || !std::strcmp(argv[1], "threads")) threads();
     std::printf("index_test: ok (%s)\n", both ? "exact, threads" : argv[1]);
     return 0;

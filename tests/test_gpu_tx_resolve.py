@@ -235,6 +235,52 @@ def test_steady_hosts_never_miss_while_another_stream_updates(engine):
         assert t.count() == (48 + len(state), 0)
 
 
+def test_one_update_larger_than_the_staging(engine):
+    """2 * 4096 + 1 puts in one call go to the device in three launches through the two staging
+    buffers (the third waits for the first); then 4097 deletions and 4097 puts of other addresses in
+    one call, two launches each. Neither call reaches the rebuild threshold (3/4 of 65536 slots).
+    After each, one launch resolves all 8193 + 4097 addresses: device = host = model."""
+    import torch
+
+    first = [f"10.{64 + (k >> 16)}.{(k >> 8) & 255}.{k & 255}" for k in range(256, 256 + 8193)]
+    others = [f"fd00:1::1:{k:x}" for k in range(1, 4098)]
+    own = ("10.64.0.7/10", "fd00:1::7/64")
+    pk, arena = _dst_batch(first + others)
+    n = len(pk)
+    model = M.Model()
+    model.set_own(own)
+
+    def check(t, d_in):
+        d_pk = _up(engine, pk)
+        d_fw, d_st = _outputs(engine, n)
+        t.resolve_device(d_pk, d_in, d_fw, d_st)
+        torch.cuda.synchronize()
+        host_pk = pk.copy()
+        h_fw, h_st = t.resolve_host(host_pk, arena)
+        want = [model.resolve(arena[int(p["in_off"]):int(p["in_off"]) + int(p["len"])].tobytes()) for p in pk]
+        got = d_pk.cpu().numpy().view(TX_PACKET_DTYPE)["tunnel"].tolist()
+        assert got == host_pk["tunnel"].tolist() == [w[0] for w in want]
+        assert d_st.cpu().numpy().tolist() == h_st.tolist() == [w[1] for w in want]
+        assert d_fw.cpu().numpy().tobytes() == h_fw.tobytes() == b"".join(w[2] for w in want)
+        return got
+
+    with TxTable(engine, 16384) as t:
+        t.set_own(own)
+        d_in = _up(engine, arena)
+        put = [(a, k + 1) for k, a in enumerate(first)]
+        t.update_hosts([], put)
+        model.update_hosts([], put)
+        got = check(t, d_in)
+        assert got == list(range(1, 8194)) + [M.NO_TUNNEL_INDEX] * 4097 and t.count() == (8193, 0)
+        put = [(a, 100000 + k) for k, a in enumerate(others)]
+        t.update_hosts(first[:4097], put)
+        model.update_hosts(first[:4097], put)
+        got = check(t, d_in)
+        assert got == [M.NO_TUNNEL_INDEX] * 4097 + list(range(4098, 8194)) + list(range(100000, 104097))
+        assert t.count() == (8193, 0)
+        assert t.probe(first[0])[0] is False and t.probe(others[0])[0] is True
+
+
 def test_routes_replaced_from_another_thread_under_load(engine):
     """set_routes from a host thread while resolves are enqueued: every batch equals the model under
     the old set or under the new set, entirely; the first batch after the call returns sees the new

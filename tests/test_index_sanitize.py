@@ -1,6 +1,7 @@
 """CPU: the index table's rules, host table and host form (index_core.hpp, index.cpp) under
 sanitizers — tests/sanitize_index builds a stand-alone program with g++ (no HIP, nothing preloaded):
-the ASan + UBSan build runs random updates and the host resolve on exact-size buffers (and the
+the ASan + UBSan build runs random updates and the host resolve on exact-size buffers, del + put +
+re-put calls slot by slot against a linear-scan model across the rebuild threshold (and the
 threads once), the TSan build runs four updating threads against two resolving ones and checks that
 a steady key never misses."""
 import os

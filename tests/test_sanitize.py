@@ -2,7 +2,8 @@
 builds window_core.hpp (replay window, exact receive rounds, thread pool) and queue_core.hpp (the
 submission queue, on a CPU device running the oracle) and workspace.hpp (the device workspaces'
 event and stream protocol, on a fake device that logs the calls) and hip_owned.hpp (the owned
-buffers' growth, moves and release, on such a fake too) and pipe_core.hpp (the staged host
+buffers' growth, moves and release, on such a fake too) and table_mirror.hpp (the lookup tables'
+two device images, staging and events, on such a fake too) and pipe_core.hpp (the staged host
 pipeline's chunk plan, chunk spans and overlap test, against brute force) with ASan+UBSan and with
 TSan and runs them; the first two also check their results against the packet-by-packet receive /
 the oracle."""
@@ -24,3 +25,4 @@ def test_sanitizer_builds_run_clean():
     assert r.stdout.count("workspace_test: ok") == 2, r.stdout
     assert r.stdout.count("pipe_test: ok") == 2, r.stdout
     assert r.stdout.count("owned_test: ok") == 2, r.stdout
+    assert r.stdout.count("mirror_test: ok") == 2, r.stdout

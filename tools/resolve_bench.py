@@ -13,6 +13,12 @@ indexes in the table: 1:0 and 4096:64. Measures, per algorithm and shape:
                      lane per packet and one header read each
   d_host_form        neb_rx_resolve_batch_host on one thread: CPU time of the GPU box's host, the
                      order of magnitude of the lookups the caller made before
+  u_update           neb_index_table_update replacing four live tunnels (others every call), back to back on one
+                     stream:
+                     wall time of the calling thread per call (the launch through pinned staging,
+                     the events), and
+  u_rebuild          the same for the calls among them that rebuild the table (they block); only on
+                     request (--measures u) and on tables of at least four tunnels
 
 Every figure is the median over windows of at least --window seconds of timed work (device events;
 d: a host clock). The two variants of a comparison alternate in one run. The b forms get fresh
@@ -51,6 +57,27 @@ def headers(subtype, remote_index, counters):
     return h
 
 
+def timed_updates(call, nput, live, slots, window, windows):
+    """us of wall time per call of an update that puts nput records over live keys, in `windows`
+    windows of at least `window` seconds of calls: ([per small update], [per rebuilding call]). The
+    kinds are told apart by the tables' own rule: a call rebuilds when live + tombstones + puts
+    pass 3/4 of the slots, and leaves the live records alone. `live`: also what the table holds now."""
+    used, small, rebuilt = live, [], []
+    for _ in range(windows):
+        ns, calls = [0, 0], [0, 0]
+        while sum(ns) < window * 1e9 or not calls[1]:
+            k = int(used + nput > slots // 4 * 3)
+            t0 = time.perf_counter_ns()
+            rc = call()
+            ns[k] += time.perf_counter_ns() - t0
+            calls[k] += 1
+            L.check(rc, "update")
+            used = live if k else used + nput
+        small.append(ns[0] / 1e3 / calls[0])
+        rebuilt.append(ns[1] / 1e3 / calls[1])
+    return small, rebuilt
+
+
 class Case:
     def __init__(self, eng, alg, n, ntun, nrelay, seed=1):
         import torch
@@ -78,6 +105,7 @@ class Case:
         rows["key_id"][ntun:], rows["flags"][ntun:] = self.kid[np.arange(nrelay) % ntun], L.VIA_TERMINAL
         rows["tunnel"] = L.RELAY_NONE
         self.table.update([], rows)
+        self.entries = rows
         self.h_arena = rng.integers(0, 256, n * STRIDE, dtype=np.uint8)
         self.arena = torch.from_numpy(self.h_arena).to(self.dev)
         self.rows = self.arena.view(n, STRIDE)
@@ -145,6 +173,14 @@ class Case:
         L.check(lib.neb_rx_resolve_batch(*ra), "neb_rx_resolve_batch")
         L.check(lib.neb_rx_plain_from_wire(*pa), "neb_rx_plain_from_wire")
         return (lambda: lib.neb_rx_resolve_batch(*ra)), (lambda: lib.neb_rx_plain_from_wire(*pa))
+
+    def bare_update(self):
+        """neb_index_table_update putting four tunnels' own records again, four others every call."""
+        groups = [self.entries[k:k + 4].copy() for k in range(0, self.ntun - 3, 4)]
+        s = C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+        args = [(self.table.handle, None, 0, g.ctypes.data_as(C.c_void_p), 4, s) for g in groups]
+        turn = iter(range(1 << 62))
+        return lambda: L.lib().neb_index_table_update(*args[next(turn) % len(args)])
 
     def check(self):
         """The device resolve, the caller's arrays and the host form agree; the batch opens."""
@@ -274,6 +310,14 @@ def main():
                                     calls += 1
                                 ws.append((time.perf_counter() - t0) * 1e6 / calls)
                             emit(case, alg_name, "d_host_form", mix, ws, clock="CPU time of the GPU box's host, one thread")
+                    if "u" in measures and ntun >= 4:  # last: it leaves tombstones behind
+                        live = ntun + nrelay
+                        small, rebuilt = timed_updates(case.bare_update(), 4, live, max(16, 1 << (4 * live - 1).bit_length()),
+                                                       a.window, a.windows)
+                        torch.cuda.synchronize()
+                        emit(case, alg_name, "u_update", "replace_4", small, clock="wall time of the calling thread")
+                        emit(case, alg_name, "u_rebuild", "replace_4", rebuilt, clock="wall time of the calling thread")
+                        case.check()  # the table still resolves as before
                 finally:
                     case.close()
     if a.out:

@@ -14,6 +14,11 @@ falls to a route and its ECMP bucket; the gateway's host entry gives the tunnel)
   b_resolve_seal     the resolve, then the same seal on the tunnels it wrote, on one stream
   c_host_form        neb_tx_resolve_batch_host on one thread of this box's CPU, on the same batch, into
                      output arrays allocated once (wall time per call)
+  u_update, u_rebuild  neb_tx_table_update_hosts replacing four live hosts (others every call), back to back on one
+                     stream:
+                     wall time of the calling thread per call, and per call that rebuilds (as
+                     tools/resolve_bench.py); only on request (--measures u), plain in_network reads,
+                     tables of at least four hosts
 
 Every figure is the median over windows of at least --window seconds of timed work (device events;
 c: a host clock). The variants of a comparison alternate in one run. Before timing, the device
@@ -40,6 +45,7 @@ from nebula_amd import _lib as L  # noqa: E402
 from nebula_amd.hostmap import IndexTable, TxTable, tx_hosts, tx_routes  # noqa: E402
 from nebula_amd.inside import TX_PACKET_DTYPE, TX_TUNNEL_DTYPE, DeviceTxBatch, slot_bytes  # noqa: E402
 from nebula_amd.noiseutil import Engine  # noqa: E402
+from resolve_bench import timed_updates  # noqa: E402
 
 MSS, PER, PLAIN = 1448, 45, 1300
 
@@ -159,6 +165,15 @@ class Case:
         return {"a_tx_resolve_fw": lambda: lib.neb_tx_resolve_batch(*fw), "a_tx_resolve": lambda: lib.neb_tx_resolve_batch(*nofw),
                 "a_rx_resolve": lambda: lib.neb_rx_resolve_batch(*rx)}
 
+    def bare_update(self):
+        """neb_tx_table_update_hosts putting four hosts' own tunnels again, four others every call."""
+        groups = [tx_hosts([(str(ipaddress.ip_address(0x0A010000 + h)), h) for h in range(k, k + 4)])
+                  for k in range(0, self.nhosts - 3, 4)]
+        s = C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+        args = [(self.table.handle, None, 0, g.ctypes.data_as(C.c_void_p), 4, s) for g in groups]
+        turn = iter(range(1 << 62))
+        return lambda: L.lib().neb_tx_table_update_hosts(*args[next(turn) % len(args)])
+
     def check(self):
         """The device resolve equals the caller-filled tunnels and the host form; both seals agree."""
         t = self.torch
@@ -243,6 +258,14 @@ def main():
                                     res[k].append(case.timed_launches(fn, a.window))
                             for k, v in res.items():
                                 emit(case, k, [u for u, _ in v], launches_per_window=v[-1][1])
+                        if "u" in measures and kind == "plain" and mix == "in_network" and nhosts >= 4:
+                            live, cap = nhosts + nroutes, nhosts + max(nroutes, 1)
+                            small, rebuilt = timed_updates(case.bare_update(), 4, live, max(16, 1 << (4 * cap - 1).bit_length()),
+                                                           a.window, a.windows)
+                            torch.cuda.synchronize()
+                            emit(case, "u_update", small, clock="wall time of the calling thread")
+                            emit(case, "u_rebuild", rebuilt, clock="wall time of the calling thread")
+                            case.check()  # the table still resolves as before
                         if "b" in measures:  # alternating, step by step, until each form has its windows
                             forms = {"b_seal": case.filled.seal, "b_resolve_seal": case.resolve_seal}
                             done, acc, warm = {f: [] for f in forms}, {f: [0.0, 0] for f in forms}, 3
