@@ -1,8 +1,11 @@
 // engine.cpp — host side of the C ABI in include/nebula_aead.h.
 //
 // Owns one HIP device per engine: its stream, the device key table, pinned staging for the
-// per-packet CipherState calls, and the double-buffered host-resident batch pipeline. All packet
-// arithmetic runs in the gfx950 kernels (aes_gcm.hip, chacha_poly.hip); there is no CPU path.
+// per-packet CipherState calls, the staged host-resident batch pipeline (Pipe) and the host
+// receive's staging (neb::RxStaging). Every seal or open of a batch, whatever path asks for it, is
+// one launch_batch over a neb::BatchLaunch (engine_internal.hpp), which window.cpp and queue.cpp
+// reach through neb_launch. All packet arithmetic runs in the gfx950 kernels (aes_gcm.hip,
+// chacha_poly.hip); there is no CPU path.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,6 +55,7 @@ struct SchedSpace {
 namespace {
 
 constexpr size_t kStageMin = 1 << 16;
+using neb::BatchLaunch;
 using neb::DevBuf;
 using neb::PinnedBuf;
 using neb::kCombMax;  // cipher.hpp
@@ -226,21 +230,17 @@ struct neb_engine {
     TxSpace tx;
     CoSpace co;
 
-    // Pipelined batched receive (window.cpp): each chunk's open on a stream (and mixed-key
-    // workspace) of its own, so consecutive chunks overlap on the device; descriptors and statuses
-    // staged in pinned memory; one event per chunk.
-    struct RxSlot {
-        neb::Stream stream;
-        neb::Event ev;
-        SchedSpacePtr sched;
-    };
+    // The host receive's zero-copy open (neb::RxStaging, window.cpp): a stream and mixed-key
+    // workspace of its own, descriptors and statuses staged in pinned memory, one event.
     struct RxSpace {
-        std::mutex mu;  // held from neb_rx_pipe_begin to neb_rx_pipe_end
+        std::mutex mu;  // held for the lifetime of a neb::RxStaging
         PinnedBuf<neb_desc> h_desc;
         PinnedBuf<int32_t> h_status;
         DevBuf<neb_desc> d_desc;
         DevBuf<int32_t> d_status;
-        std::vector<RxSlot> slot;
+        neb::Stream stream;
+        neb::Event ev;
+        SchedSpace sched;
     } rx;
 
 };
@@ -479,7 +479,7 @@ NEB_API int neb_engine_destroy(neb_engine* e) {
     DeviceGuard dg(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     e->pipe.drain();
-    for (auto& r : e->rx.slot) hipStreamSynchronize(r.stream);  // (a slot in the list is complete)
+    if (e->rx.stream) hipStreamSynchronize(e->rx.stream);
     for (PktSlot& sl : e->pkt.slot)
         if (sl.stream) hipStreamSynchronize(sl.stream);
     delete e;
@@ -786,36 +786,33 @@ static uint32_t front_groups(const neb_engine* e, uint32_t n) {
     return below > 0 && cap > 0 && (uint64_t)n < (uint64_t)below * waves ? (uint32_t)std::min<int64_t>(cap, 8) : 8u;
 }
 
-// d_n (optional): the batch's real packet count in device memory, at most n (a batch whose size is
-// only known on the device, e.g. the segments of a TX batch). hdr_from_dst: the TX batch's
-// descriptors (tx.hip) read their first `flags` plaintext bytes from the destination.
-// rx (optional, opens only): the device receive's admission mask; only packets with rx[i] != 0 are
-// opened, the others keep the statuses its plan wrote (window.cpp, rxwin.hip).
-// prebinned: the mixed-key binning of this batch is already in `sched` (neb_prebin, ordered before s).
-static hipError_t launch_batch(neb_engine* e, int alg, int open, const neb_desc* d_desc, uint32_t n, uint8_t* d_arena,
-                               int32_t* d_status, uint32_t key_hint, hipStream_t s, const uint32_t* d_n = nullptr,
-                               SchedSpace* sched = nullptr, int hdr_from_dst = 0, hipEvent_t stop = nullptr,
-                               const uint8_t* rx = nullptr, bool prebinned = false) {
-    if (alg == NEB_ALG_AESGCM) {
-        if (key_hint != NEB_KEYS_MIXED)
-            return neb_gcm_batch_single(open, d_desc, n, d_arena, e->d_keys, e->max_keys, key_hint, d_status, d_n,
-                                        e->cu_count, s, hdr_from_dst, stop, rx);
+// One seal or open of a batch (neb::BatchLaunch, engine_internal.hpp). b.d_n: a batch whose size is
+// only known on the device, e.g. the segments of a TX batch. b.rx: only packets with rx[i] != 0 are
+// opened, the others keep the statuses the receive's plan wrote (window.cpp, rxwin.hip).
+// b.prebinned: the mixed-key binning of this batch is already in b.sched (neb_rx_sched_begin,
+// ordered before b.stream).
+static hipError_t launch_batch(neb_engine* e, const BatchLaunch& b) {
+    hipStream_t s = b.stream;
+    if (b.alg == NEB_ALG_AESGCM) {
+        if (b.key_hint != NEB_KEYS_MIXED)
+            return neb_gcm_batch_single(b.open, b.desc, b.n, b.arena, e->d_keys, e->max_keys, b.key_hint, b.status,
+                                        b.d_n, e->cu_count, s, b.hdr_from_dst, b.stop, b.rx);
         // mixed keys: regroup into single-key, similar-size chunks on the device, then seal/open
-        SchedSpace& sp = sched ? *sched : e->sched;
+        SchedSpace& sp = b.sched ? *b.sched : e->sched;
         std::lock_guard<std::mutex> g(sp.mu);
         hipError_t err = hipSuccess;
-        if (!prebinned) {
-            err = sched_reserve(e, sp, n, s);
+        if (!b.prebinned) {
+            err = sched_reserve(e, sp, b.n, s);
             if (err == hipSuccess) err = sp.dev.begin(s);  // after the previous batch on it
             neb::SchedWs ws = sp.ws;
-            ws.max_groups = front_groups(e, n);
-            if (err == hipSuccess) err = neb_sched_build(d_desc, n, d_n, e->max_keys, 4u, &ws, s);
+            ws.max_groups = front_groups(e, b.n);
+            if (err == hipSuccess) err = neb_sched_build(b.desc, b.n, b.d_n, e->max_keys, 4u, &ws, s);
         }
         if (err == hipSuccess)  // the workspace's event bound to the chunk kernel's dispatch: no marker packet between batches
-            err = neb_gcm_batch_chunked(open, d_desc, n, d_arena, e->d_keys, e->max_keys, d_status, sp.ws.sorted,
+            err = neb_gcm_batch_chunked(b.open, b.desc, b.n, b.arena, e->d_keys, e->max_keys, b.status, sp.ws.sorted,
                                         sp.ws.chunks, sp.ws.counters, sp.ws.max_chunks, e->cu_count,
-                                        s, hdr_from_dst, sp.dev.event(),
-                                        prebinned ? nullptr : rx);  // (prebinned: refused packets unlisted)
+                                        s, b.hdr_from_dst, sp.dev.event(),
+                                        b.prebinned ? nullptr : b.rx);  // (prebinned: refused packets unlisted)
         if (err == hipSuccess) {
             sp.dev.end_bound(s);
         } else {
@@ -826,8 +823,8 @@ static hipError_t launch_batch(neb_engine* e, int alg, int open, const neb_desc*
         }
         return err;
     }
-    return neb_chacha_batch(open, d_desc, n, d_arena, e->d_keys, e->max_keys, key_hint, d_status, d_n, e->cu_count,
-                            s, hdr_from_dst, stop, rx);
+    return neb_chacha_batch(b.open, b.desc, b.n, b.arena, e->d_keys, e->max_keys, b.key_hint, b.status, b.d_n,
+                            e->cu_count, s, b.hdr_from_dst, b.stop, b.rx);
 }
 
 // Poll a per-packet call's status word in pinned host memory (-1 until the kernel publishes it) for up
@@ -920,8 +917,8 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
     *(int32_t*)(h + o_status) = -1;
     if (ad_len) std::memcpy(h + o_aad, ad, ad_len);
     if (in_len) std::memcpy(h + o_pay, in, in_len);
-    err = launch_batch(e, c->alg, open, (const neb_desc*)(h + o_desc), 1, h + o_aad, (int32_t*)(h + o_status),
-                       c->key_id, sl->stream);
+    err = launch_batch(e, {.alg = c->alg, .open = open, .desc = (const neb_desc*)(h + o_desc), .n = 1, .arena = h + o_aad,
+                           .status = (int32_t*)(h + o_status), .key_hint = c->key_id, .stream = sl->stream});
     if (err == hipSuccess) err = hipStreamSynchronize(sl->stream);
     if (err != hipSuccess) {
         set_error("one_packet", err);
@@ -1120,7 +1117,8 @@ static int batch_device(neb_engine* e, int alg, int open, const neb_desc* d_desc
     // neb_cipher_destroy waits on that event, so it needs no key-use event of its own.
     const bool sched = alg == NEB_ALG_AESGCM && key_hint == NEB_KEYS_MIXED;
     hipEvent_t stop = sched ? nullptr : use_event(e, key_hint, s);
-    hipError_t err = launch_batch(e, alg, open, d_desc, n, d_arena, d_status, key_hint, s, nullptr, nullptr, 0, stop);
+    hipError_t err = launch_batch(e, {.alg = alg, .open = open, .desc = d_desc, .n = n, .arena = d_arena,
+                                      .status = d_status, .key_hint = key_hint, .stream = s, .stop = stop});
     if (err != hipSuccess) {
         set_error("batch launch", err);
         return NEB_ERR_HIP;
@@ -1144,47 +1142,35 @@ NEB_API int neb_open_batch(neb_engine* e, int alg, const neb_desc* d_desc, uint3
 int neb_engine_device_of(const neb_engine* e) { return e->device; }
 int neb_check_batch_args(neb_engine* e, int alg, uint32_t key_hint) { return check_batch(e, alg, key_hint); }
 
-// Open the first *d_n (a count in device memory) of at most n descriptors, on stream s.
-int neb_open_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
-                         uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s, const uint8_t* rx,
-                         SchedSpace* prebinned) {
-    if (n == 0) return NEB_OK;
-    hipError_t err = launch_batch(e, alg, 1, d_desc, n, d_arena, d_status, key_hint, s, d_n, prebinned, 0, nullptr,
-                                  rx, prebinned != nullptr);
+// The launch of window.cpp (the device receive's opens, the relay forwarding's seal) and queue.cpp
+// (one staged batch, zero-copy on pinned memory, on the queue's stream); the caller has made the
+// engine's device current.
+int neb_launch(neb_engine* e, const BatchLaunch& b) {
+    if (b.n == 0) return NEB_OK;
+    hipError_t err = launch_batch(e, b);
     if (err != hipSuccess) {
         set_error("batch launch", err);
         return NEB_ERR_HIP;
     }
+    if (b.note_use) note_use(e, b.key_hint, b.stream);
     return NEB_OK;
 }
 
-// Relay forwarding (window.cpp, relay.hip): the key table its plan checks the tunnels' keys against,
-// and the seal of the first *d_n (a count in device memory) of at most n descriptors on stream s.
+// Relay forwarding (window.cpp, relay.hip): the key table its plan checks the tunnels' keys against.
 void neb_engine_key_table(const neb_engine* e, const uint32_t** d_keys, uint32_t* max_keys) {
     *d_keys = e->d_keys;
     *max_keys = e->max_keys;
 }
-int neb_seal_batch_count(neb_engine* e, int alg, const neb_desc* d_desc, uint32_t n, const uint32_t* d_n,
-                         uint8_t* d_arena, int32_t* d_status, uint32_t key_hint, hipStream_t s) {
-    if (n == 0) return NEB_OK;
-    hipError_t err = launch_batch(e, alg, 0, d_desc, n, d_arena, d_status, key_hint, s, d_n);
-    if (err != hipSuccess) {
-        set_error("batch launch", err);
-        return NEB_ERR_HIP;
-    }
-    note_use(e, key_hint, s);
-    return NEB_OK;
-}
 
-// For the submission queue (queue.cpp): a scheduler workspace of its own, and a launch of one
-// staged batch (zero-copy on pinned memory) on the queue's stream.
+// A scheduler workspace of its own for each of the submission queue's batches (queue.cpp) and for
+// the device receive (window.cpp).
 SchedSpace* neb_sched_space_new() { return new (std::nothrow) SchedSpace; }
 void neb_sched_space_free(SchedSpace* sp) { delete sp; }  // ~DevWorkspace waits for the last batch on it
 
 // The device receive (window.cpp): its mixed-key AES-GCM open is binned by extra workgroups of the
 // receive's own plan launches (rxwin.hpp RxBin) into the receive's scheduler workspace `sched`,
 // which this sizes for n packets and orders after its last open; the open then runs with it
-// (neb_open_batch_count's `prebinned`). neb_rx_sched_abort after a failed plan (the counters are
+// (BatchLaunch::prebinned). neb_rx_sched_abort after a failed plan (the counters are
 // then in an unknown state: the next batch clears them).
 int neb_rx_sched_begin(neb_engine* e, uint32_t n, SchedSpace* sched, hipStream_t s, neb::SchedWs* ws,
                        uint32_t* max_keys) {
@@ -1205,17 +1191,6 @@ int neb_rx_sched_begin(neb_engine* e, uint32_t n, SchedSpace* sched, hipStream_t
 void neb_rx_sched_abort(SchedSpace* sched) {
     std::lock_guard<std::mutex> g(sched->mu);
     sched->dirty = true;
-}
-int neb_launch_on(neb_engine* e, int alg, int open, const neb_desc* desc, uint32_t n, uint8_t* arena,
-                  int32_t* status, uint32_t key_hint, hipStream_t s, SchedSpace* sched) {
-    if (n == 0) return NEB_OK;
-    DeviceGuard dg(e->device);
-    hipError_t err = launch_batch(e, alg, open, desc, n, arena, status, key_hint, s, nullptr, sched, 0, nullptr);
-    if (err != hipSuccess) {
-        set_error("queue batch launch", err);
-        return NEB_ERR_HIP;
-    }
-    return NEB_OK;
 }
 int neb_key_alg(neb_engine* e, uint32_t key) {
     std::lock_guard<std::mutex> g(e->key_mu);
@@ -1252,7 +1227,8 @@ static int batch_host_zero_copy(neb_engine* e, int alg, int open, const neb_desc
         d_desc = e->zc_desc;
     }
     if (!status_mapped) d_status = e->zc_status;
-    HIP_TRY(launch_batch(e, alg, open, d_desc, n, arena, d_status, key_hint, e->stream));
+    HIP_TRY(launch_batch(e, {.alg = alg, .open = open, .desc = d_desc, .n = n, .arena = arena, .status = d_status,
+                             .key_hint = key_hint, .stream = e->stream}));
     if (!status_mapped)
         HIP_TRY(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1377,7 +1353,8 @@ static int batch_host(neb_engine* e, int alg, int open, const neb_desc* desc, ui
         // copy-in stream the small copy's latency left that stream idle between chunks.
         PIPE_TRY(hipStreamWaitEvent(P.comp, s.in_done, 0));
         PIPE_TRY(neb_copy_desc(s.d_desc, s.h_desc, cnt, P.comp));
-        PIPE_TRY(launch_batch(e, alg, open, s.d_desc, cnt, s.d_buf, s.h_status, key_hint, P.comp, nullptr, &P.sched));
+        PIPE_TRY(launch_batch(e, {.alg = alg, .open = open, .desc = s.d_desc, .n = cnt, .arena = s.d_buf,
+                                  .status = s.h_status, .key_hint = key_hint, .stream = P.comp, .sched = &P.sched}));
         PIPE_TRY(hipEventRecord(s.k_done, P.comp));
         if (k == 0 && !check_upto(n)) {  // the rest of the batch, while chunk 0 is copied in and run
             P.drain();
@@ -1403,70 +1380,50 @@ NEB_API int neb_open_batch_host(neb_engine* e, int alg, const neb_desc* desc, ui
     return batch_host(e, alg, 1, desc, n, arena, arena_len, status, key_hint);
 }
 
-// ---- pipelined receive (window.cpp) -----------------------------------------------------------
-// The caller has validated every descriptor. begin: true = the arena is mapped pinned memory and
-// zero-copy is the host mode; the pipeline is then reserved for the caller (e->rx.mu) until end.
-// false with *rc == NEB_OK: use the synchronous neb_open_batch_host instead.
+// ---- the host receive's staging (window.cpp) --------------------------------------------------
+// neb::RxStaging (engine_internal.hpp): active when the arena is mapped pinned memory and zero-copy
+// is the host mode; e->rx is then the caller's until the object goes.
 
-bool neb_rx_pipe_begin(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena, uint32_t n, uint32_t nchunks,
-                       neb_desc** h_desc, int32_t** h_status, int* rc) {
-    *rc = check_batch(e, alg, key_hint);
-    if (*rc != NEB_OK || n == 0 || host_mode() != kHostZeroCopy || !host_mapped(arena)) return false;
+neb::RxStaging::RxStaging(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena, uint32_t n)
+    : alg_(alg), rc_(check_batch(e, alg, key_hint)), key_hint_(key_hint), arena_(arena) {
+    if (rc_ != NEB_OK || n == 0 || host_mode() != kHostZeroCopy || !host_mapped(arena)) return;
     auto& r = e->rx;
-    r.mu.lock();
+    std::unique_lock<std::mutex> lk(r.mu);
     hipSetDevice(e->device);
-    auto fail = [&] {
-        r.mu.unlock();
-        *rc = NEB_ERR_HIP;
-        return false;
-    };
-    while (r.slot.size() < nchunks) {
-        neb_engine::RxSlot sl;
-        sl.sched.reset(neb_sched_space_new());
-        // the kernels' stores into the mapped arena must be visible to the host at the event
-        if (!sl.sched || sl.stream.create(hipStreamNonBlocking) != hipSuccess ||
-            sl.ev.create(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess)
-            return fail();
-        r.slot.push_back(std::move(sl));
-    }
-    auto idle = [&] {  // before a staging buffer is freed: nothing queued on any slot's stream
-        hipError_t err = hipSuccess;
-        for (size_t k = 0; k < r.slot.size() && err == hipSuccess; k++) err = hipStreamSynchronize(r.slot[k].stream);
-        return err;
-    };
+    rc_ = NEB_ERR_HIP;
+    // the kernels' stores into the mapped arena must be visible to the host at the event
+    if (r.stream.create(hipStreamNonBlocking) != hipSuccess ||
+        r.ev.create(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess)
+        return;
+    // a staging buffer is freed (to grow) only with the receive stream idle: nothing queued reads it
+    auto idle = [&] { return hipStreamSynchronize(r.stream); };
     if (r.h_desc.reserve((size_t)n * sizeof(neb_desc), nullptr, idle) != hipSuccess ||
         r.h_status.reserve((size_t)n * sizeof(int32_t), nullptr, idle) != hipSuccess ||
         r.d_desc.reserve((size_t)n * sizeof(neb_desc), nullptr, idle) != hipSuccess ||
         r.d_status.reserve((size_t)n * sizeof(int32_t), nullptr, idle) != hipSuccess)
-        return fail();
-    *h_desc = r.h_desc;
-    *h_status = r.h_status;
-    return true;
+        return;
+    rc_ = NEB_OK;
+    desc_ = r.h_desc;
+    status_ = r.h_status;
+    e_ = e;
+    lk.release();  // held until ~RxStaging
 }
 
-// Queue chunk k: descriptors [c0, c0 + cnt) of the staging buffer, opened zero-copy in the arena.
-int neb_rx_pipe_submit(neb_engine* e, int alg, uint32_t key_hint, uint8_t* arena, uint32_t c0, uint32_t cnt,
-                       uint32_t k) {
-    auto& r = e->rx;
-    auto& sl = r.slot[k];
-    HIP_TRY(hipMemcpyAsync(r.d_desc + c0, r.h_desc + c0, (size_t)cnt * sizeof(neb_desc), hipMemcpyHostToDevice,
-                           sl.stream));
-    HIP_TRY(launch_batch(e, alg, 1, r.d_desc + c0, cnt, arena, r.d_status + c0, key_hint, sl.stream, nullptr,
-                         sl.sched.get()));
-    HIP_TRY(hipMemcpyAsync(r.h_status + c0, r.d_status + c0, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost,
-                           sl.stream));
-    HIP_TRY(hipEventRecord(sl.ev, sl.stream));
+int neb::RxStaging::open(uint32_t cnt) {
+    auto& r = e_->rx;
+    HIP_TRY(hipMemcpyAsync(r.d_desc, r.h_desc, (size_t)cnt * sizeof(neb_desc), hipMemcpyHostToDevice, r.stream));
+    HIP_TRY(launch_batch(e_, {.alg = alg_, .open = 1, .desc = r.d_desc, .n = cnt, .arena = arena_, .status = r.d_status,
+                              .key_hint = key_hint_, .stream = r.stream, .sched = &r.sched}));
+    HIP_TRY(hipMemcpyAsync(r.h_status, r.d_status, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_TRY(hipEventRecord(r.ev, r.stream));
+    HIP_TRY(hipEventSynchronize(r.ev));
     return NEB_OK;
 }
 
-int neb_rx_pipe_wait(neb_engine* e, uint32_t k) {
-    HIP_TRY(hipEventSynchronize(e->rx.slot[k].ev));
-    return NEB_OK;
-}
-
-void neb_rx_pipe_end(neb_engine* e) {
-    for (auto& sl : e->rx.slot) hipStreamSynchronize(sl.stream);
-    e->rx.mu.unlock();
+neb::RxStaging::~RxStaging() {
+    if (!e_) return;
+    hipStreamSynchronize(e_->rx.stream);
+    e_->rx.mu.unlock();
 }
 
 // ---- transmit batch (tx.hip) ------------------------------------------------------------------
@@ -1513,15 +1470,17 @@ static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, c
     const uint32_t cs_slots = cs ? neb_gcm_single_slots(max_wires, e->cu_count, 0, 2) : 0u;
     HIP_TRY(neb_tx_segment(d_pk, npk, d_in, d_tun, d_via, d_out, &tx.ws, d_wires, d_nwires, max_wires, e->cu_count,
                            cs_slots, s));
-    HIP_TRY(launch_batch(e, alg, 0, tx.ws.seal_desc, max_wires, d_out, d_wire_status, key_hint, s, d_nwires, nullptr,
-                         cs ? 2 : 1));  // hdr_from_dst: the seal reads the payload from the TUN read
+    HIP_TRY(launch_batch(e, {.alg = alg, .open = 0, .desc = tx.ws.seal_desc, .n = max_wires, .d_n = d_nwires,
+                             .arena = d_out, .status = d_wire_status, .key_hint = key_hint, .stream = s,
+                             .hdr_from_dst = cs ? 2 : 1}));  // the seal reads the payload from the TUN read
     HIP_TRY(neb_tx_finish(d_tun, npk, ntun, &tx.ws, s));
     if (d_via && max_wires) {
         // prepareSendVia's tags: the AD-only seal over the compacted via wires, behind the inner seal
         HIP_TRY(hipEventSynchronize(tx.via_ev));
         uint32_t hint = *tx.h_via_key;
         if (hint != NEB_KEYS_MIXED && check_batch(e, alg, hint) != NEB_OK) hint = NEB_KEYS_MIXED;
-        HIP_TRY(launch_batch(e, alg, 0, tx.ws.via_desc, max_wires, d_out, tx.ws.via_status, hint, s, tx.ws.nvia));
+        HIP_TRY(launch_batch(e, {.alg = alg, .open = 0, .desc = tx.ws.via_desc, .n = max_wires, .d_n = tx.ws.nvia,
+                                 .arena = d_out, .status = tx.ws.via_status, .key_hint = hint, .stream = s}));
         HIP_TRY(neb_tx_via_fix(&tx.ws, max_wires, d_wire_status, s));
         note_use(e, hint, s);
     }
@@ -1805,14 +1764,8 @@ static int batch_host_multi(neb_engine* const* engines, uint32_t m, int alg, int
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t b = shard_lo(n, k, m), c = shard_lo(n, k + 1, m) - b;
             if (c == 0 || skip[k]) continue;
-            uint64_t lo = ~0ULL, hi = 0;
-            for (uint32_t i = b; i < b + c; i++) {
-                const neb_desc& d = desc[i];
-                const uint64_t pay = (uint64_t)d.len + (open ? 16u : 0u), outl = (uint64_t)d.len + (open ? 0u : 16u);
-                lo = std::min({lo, d.src_off, d.dst_off, d.aad_off});
-                hi = std::max({hi, d.src_off + pay, d.dst_off + outl, d.aad_off + d.aad_len});
-            }
-            span.push_back({lo & ~(uint64_t)15, hi});
+            const neb::PipeSpan sp = neb::pipe_span(desc + b, c, open);
+            span.push_back({sp.lo, sp.hi});
         }
         std::sort(span.begin(), span.end());
         for (size_t i = 1; i < span.size(); i++)

@@ -31,7 +31,9 @@ struct HipDev {
     std::vector<Slot> slot;
     int launch(uint32_t i, neb_desc* desc, uint32_t n, uint8_t* arena, int32_t* status, uint32_t hint, Token& tok) {
         tok = i;
-        return neb_launch_on(e, alg, open, desc, n, arena, status, hint, slot[i].stream, slot[i].sched.get());
+        DeviceGuard dg(neb_engine_device_of(e));  // (the flusher thread launches)
+        return neb_launch(e, {.alg = alg, .open = open, .desc = desc, .n = n, .arena = arena, .status = status,
+                              .key_hint = hint, .stream = slot[i].stream, .sched = slot[i].sched.get()});
     }
     int wait(Token& tok) { return hipStreamSynchronize(slot[tok].stream) == hipSuccess ? NEB_OK : NEB_ERR_HIP; }
     bool key_ok(uint32_t key) { return neb_key_alg(e, key) == alg; }

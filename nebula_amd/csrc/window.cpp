@@ -22,11 +22,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
+#include <array>
 #include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,6 +45,27 @@ struct neb_window {
     WindowCore core;
     mutable std::mutex mu;  // ConnectionState.decryptLock (connection_state.go:100,112)
 };
+
+namespace {
+
+struct RxProf {  // NEB_RX_PROF: the receives' phase times to stderr
+    using T = std::chrono::steady_clock::time_point;
+    static bool on() {
+        static const bool v = std::getenv("NEB_RX_PROF") != nullptr;
+        return v;
+    }
+    static T now() { return std::chrono::steady_clock::now(); }
+    static double us(T a, T b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
+};
+
+// every wire packet inside the arena (sums cannot wrap)
+bool wire_in_arena(const neb_rx_packet* pk, uint32_t n, size_t arena_len) {
+    for (uint32_t i = 0; i < n; i++)
+        if (pk[i].off > arena_len || neb_rx_len(pk[i]) > arena_len - pk[i].off) return false;
+    return true;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -107,238 +125,119 @@ NEB_API int neb_window_reset_counters(neb_window* w) {
     return NEB_OK;
 }
 
+// Step 2 of neb_rx_open_batch_host: one GPU open for everything the simulation lets through (plan),
+// compacted in arrival order into the engine's pinned staging (a zero-copy arena, opened on the
+// receive stream) or a private vector (any other arena: neb_open_batch_host). verd[i]: admitted
+// packet i's verdict; *ts, *td: the open's start and end.
+static int open_admitted(neb_engine* e, int alg, const neb_desc* desc, uint32_t n, uint8_t* arena, size_t arena_len,
+                         uint32_t key_hint, const uint8_t* plan, int32_t* verd, RxProf::T* ts, RxProf::T* td) {
+    neb::RxStaging stage(e, alg, key_hint, arena, n);
+    if (!stage.active() && stage.rc() != NEB_OK) return stage.rc();
+    std::vector<uint32_t> sub_of(n);
+    std::vector<neb_desc> sub;
+    std::vector<int32_t> sub_status;
+    const uint32_t ngpu = compact_admitted(desc, plan, n, sub_of.data(), [&](uint32_t m) {
+        if (stage.active()) return stage.desc();
+        sub.resize(m);
+        sub_status.assign(m, NEB_STATUS_BAD_KEY);
+        return sub.data();
+    });
+    int rc = NEB_OK;
+    *ts = RxProf::now();
+    if (ngpu)
+        rc = stage.active() ? stage.open(ngpu)
+                            : neb_open_batch_host(e, alg, sub.data(), ngpu, arena, arena_len, sub_status.data(), key_hint);
+    *td = RxProf::now();
+    // The verdicts are copied out of the staging statuses before the staging is released (on return):
+    // they are the engine's shared pinned buffer, which the next receive call on this engine (another
+    // thread) overwrites, or frees and reallocates for a larger batch, as soon as it holds rx.mu.
+    const int32_t* gst = stage.active() ? stage.status() : sub_status.data();
+    for (uint32_t i = 0; i < n && rc == NEB_OK; i++)
+        if (plan[i]) verd[i] = gst[sub_of[i]];
+    return rc;
+}
+
 NEB_API int neb_rx_open_batch_host(neb_engine* e, int alg, neb_window* const* windows, uint32_t nwindows,
                                    const neb_desc* desc, uint32_t n, uint8_t* arena, size_t arena_len,
                                    int32_t* status, uint32_t key_hint) {
     if (!e || (n && (!desc || !arena || !status || !windows))) return NEB_ERR_INVALID;
     if (n == 0) return NEB_OK;
     DeviceGuard dg;
-    static const bool prof = std::getenv("NEB_RX_PROF") != nullptr;  // phase times to stderr
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const auto now = RxProf::now;
     const auto t0 = now();
     RxPool& pool = rx_pool();
-    // packet ranges for the per-packet phases: one (measured: spread over the pool they gained
-    // nothing against the wake-ups, profiles/r2_host/rx_threads.log), the code stays range-based
-    const uint32_t nr = 1;
-    auto range = [&](uint32_t r) { return std::make_pair((uint64_t)n * r / nr, (uint64_t)n * (r + 1) / nr); };
-
-    // an invalid batch is refused before any window moves or any packet is opened
-    std::vector<uint8_t> bad(nr, 0);
-    pool.run(nr, [&](uint32_t r) {
-        const auto [i0, i1] = range(r);
-        for (uint64_t i = i0; i < i1; i++)
-            if (!neb_desc_in_arena(desc[i], 1, arena_len)) {
-                bad[r] = 1;
-                return;
-            }
-    });
-    for (uint8_t b : bad)
-        if (b) return NEB_ERR_INVALID;
-    const auto ta = now();
-    auto group_of = [&](const neb_desc& d) -> uint32_t {
-        return (d.key_id < nwindows && windows[d.key_id]) ? d.key_id : nwindows;  // nwindows: no window
+    auto with_window = [&](uint32_t g, auto&& fn) {
+        std::lock_guard<std::mutex> lk(windows[g]->mu);
+        fn(windows[g]->core);
     };
-
-    // Group by window, arrival order kept inside each (a counting sort whose ranges are counted
-    // and scattered in parallel, ranges in arrival order).
-    const uint32_t ng = nwindows + 1;
-    std::vector<uint32_t> cnt((size_t)nr * ng, 0), start(ng + 1, 0), order(n);
-    pool.run(nr, [&](uint32_t r) {
-        const auto [i0, i1] = range(r);
-        uint32_t* c = cnt.data() + (size_t)r * ng;
-        for (uint64_t i = i0; i < i1; i++) c[group_of(desc[i])]++;
-    });
-    {
-        uint32_t acc = 0;
-        for (uint32_t g = 0; g < ng; g++) {
-            start[g] = acc;
-            for (uint32_t r = 0; r < nr; r++) {
-                const uint32_t c = cnt[(size_t)r * ng + g];
-                cnt[(size_t)r * ng + g] = acc;
-                acc += c;
-            }
-        }
-        start[ng] = acc;
-    }
-    pool.run(nr, [&](uint32_t r) {
-        const auto [i0, i1] = range(r);
-        uint32_t* c = cnt.data() + (size_t)r * ng;
-        for (uint64_t i = i0; i < i1; i++) order[c[group_of(desc[i])]++] = (uint32_t)i;
-    });
+    auto par = [&](uint32_t cnt, auto&& fn) { pool.run(cnt, fn); };
+    // an invalid batch is refused before any window moves or any packet is opened
+    for (uint32_t i = 0; i < n; i++)
+        if (!neb_desc_in_arena(desc[i], 1, arena_len)) return NEB_ERR_INVALID;
+    const auto ta = now();
+    const RxGroups G = group_by_window(
+        n, nwindows, [&](uint32_t i) { return desc[i].key_id; }, [&](uint32_t g) { return windows[g] != nullptr; });
     const auto tb = now();
-    // window groups for the per-window phases: contiguous runs of windows with about equal packets,
-    // spread over the pool when the batch touches many windows (C3, 4096 tunnels: simulation 456 ->
-    // 221 us, real pass 728 -> 472 us on 8 threads); one window's packets always stay on one thread
-    uint32_t touched = 0;
-    for (uint32_t g = 0; g < nwindows; g++) touched += start[g] != start[g + 1];
-    const uint32_t nwg = touched < kRxMinWindows ? 1u
-                                                  : std::max(1u, std::min(pool.size(), start[nwindows] / kRxMinPerThread));
-    std::vector<uint32_t> wsplit(nwg + 1, nwindows);
-    {
-        wsplit[0] = 0;
-        uint32_t g = 0;
-        for (uint32_t t = 1; t < nwg; t++) {
-            const uint64_t want = (uint64_t)start[nwindows] * t / nwg;
-            while (g < nwindows && start[g + 1] <= want) g++;
-            wsplit[t] = std::max(g, wsplit[t - 1]);
-        }
-    }
-
+    const uint32_t nwg = window_group_count(G.start, nwindows, pool.size());
+    const std::vector<uint32_t> wsplit = split_windows(G.start, nwindows, nwg);
     const auto tc = now();
-    // 1. simulation on a private copy of each window: which packets would the sequential receive
-    //    path decrypt? (one scratch window per thread, reused window after window)
-    enum : uint8_t { kToGpu, kHeld };
-    std::vector<uint8_t> plan(n, kHeld);
-    pool.run(nwg, [&](uint32_t t) {
-        WindowCore sim;
-        for (uint32_t g = wsplit[t]; g < wsplit[t + 1]; g++) {
-            if (start[g] == start[g + 1]) continue;
-            {
-                std::lock_guard<std::mutex> lk(windows[g]->mu);
-                sim = windows[g]->core;
-            }
-            for (uint32_t k = start[g]; k < start[g + 1]; k++) {
-                const uint32_t i = order[k];
-                if (sim.check(desc[i].counter)) {
-                    sim.update(desc[i].counter);
-                    plan[i] = kToGpu;
-                }
-            }
-        }
-    });
+    // 1. the simulation: opened[i] = 1 for the packets the sequential receive path would decrypt
+    std::vector<uint8_t> opened = simulate_admits(G, wsplit, [&](uint32_t i) { return desc[i].counter; }, with_window, par);
     const auto t1 = now();
-
-    // 2. one GPU open for everything the simulation lets through, compacted in arrival order into
-    //    the engine's pinned staging buffer (a zero-copy arena, opened on the receive stream) or
-    //    a private vector (any other arena: neb_open_batch_host)
-    neb_desc* h_desc = nullptr;
-    int32_t* h_status = nullptr;
-    int rc = NEB_OK;
-    const bool piped = neb_rx_pipe_begin(e, alg, key_hint, arena, n, 1, &h_desc, &h_status, &rc);
-    if (!piped && rc != NEB_OK) return rc;
-    std::vector<uint32_t> sub_of(n, 0), before(nr + 1, 0);
-    pool.run(nr, [&](uint32_t r) {
-        const auto [i0, i1] = range(r);
-        uint32_t c = 0;
-        for (uint64_t i = i0; i < i1; i++) c += plan[i] == kToGpu;
-        before[r + 1] = c;
-    });
-    for (uint32_t r = 0; r < nr; r++) before[r + 1] += before[r];
-    const uint32_t ngpu = before[nr];
-    std::vector<neb_desc> sub(piped ? 0 : ngpu);
-    std::vector<int32_t> sub_status(piped ? 0 : ngpu, NEB_STATUS_BAD_KEY);
-    neb_desc* out = piped ? h_desc : sub.data();
-    pool.run(nr, [&](uint32_t r) {
-        const auto [i0, i1] = range(r);
-        uint32_t j = before[r];
-        if (before[r + 1] - j == i1 - i0) {  // every packet of the range: one copy
-            std::memcpy(out + j, desc + i0, (size_t)(i1 - i0) * sizeof(neb_desc));
-            for (uint64_t i = i0; i < i1; i++) sub_of[i] = j++;
-            return;
-        }
-        for (uint64_t i = i0; i < i1; i++)
-            if (plan[i] == kToGpu) {
-                sub_of[i] = j;
-                out[j++] = desc[i];
-            }
-    });
-    const int32_t* gst = piped ? h_status : sub_status.data();
-    const auto ts = now();
-    if (ngpu) {
-        if (piped) {
-            rc = neb_rx_pipe_submit(e, alg, key_hint, arena, 0, ngpu, 0);
-            if (rc == NEB_OK) rc = neb_rx_pipe_wait(e, 0);
-        } else {
-            rc = neb_open_batch_host(e, alg, sub.data(), ngpu, arena, arena_len, sub_status.data(), key_hint);
-        }
-    }
-    const auto td = now();
-    // The verdicts are copied out of the staging statuses before the pipeline is released: gst is
-    // the engine's shared pinned buffer, which the next receive call on this engine (another
-    // thread) overwrites, or frees and reallocates for a larger batch, as soon as it holds rx.mu.
-    std::vector<uint8_t> opened(n, 0);
+    // 2. one GPU open for them
     std::vector<int32_t> verd(n, NEB_STATUS_BAD_KEY);
-    if (rc == NEB_OK)
-        for (uint32_t i = 0; i < n; i++)
-            if (plan[i] == kToGpu) {
-                opened[i] = 1;
-                verd[i] = gst[sub_of[i]];
-            }
-    if (piped) neb_rx_pipe_end(e);
+    RxProf::T ts, td;
+    int rc = open_admitted(e, alg, desc, n, arena, arena_len, key_hint, opened.data(), verd.data(), &ts, &td);
     if (rc != NEB_OK) return rc;
     const auto t2 = now();
 
     // 3. the real windows, each in arrival order: Check → tag verdict → Update (exact_rounds: a
     //    packet held back that its window accepts is opened with the rest of its window's run)
-    for (uint32_t k = start[nwindows]; k < start[nwindows + 1]; k++) status[order[k]] = NEB_STATUS_BAD_KEY;
-    std::vector<ExactRun> runs;
-    for (uint32_t g = 0; g < nwindows; g++)
-        if (start[g] != start[g + 1]) runs.push_back({g, start[g], start[g + 1]});
+    for (uint32_t k = G.start[nwindows]; k < G.start[nwindows + 1]; k++) status[G.order[k]] = NEB_STATUS_BAD_KEY;
+    // an extra round's open of packets pk through descriptors ds over arena ar; how: opened[]'s mark
+    auto open_extra = [&](const std::vector<uint32_t>& pk, const neb_desc* ds, uint8_t* ar, size_t ar_len, uint8_t how) {
+        std::vector<int32_t> st(pk.size(), NEB_STATUS_BAD_KEY);
+        const int r = neb_open_batch_host(e, alg, ds, (uint32_t)pk.size(), ar, ar_len, st.data(), key_hint);
+        for (size_t j = 0; j < pk.size() && r == NEB_OK; j++) {
+            opened[pk[j]] = how;
+            verd[pk[j]] = st[j];
+        }
+        return r;
+    };
     // speculative verifications (exact_rounds' later rounds): each packet's AAD and ciphertext+tag
     // copied into a private arena and opened there; pt_at[i] = its plaintext's offset in it
     std::vector<uint8_t> spec;
     std::vector<uint64_t> pt_at;
     std::vector<uint32_t> commit, zero;
     rc = exact_rounds(
-        runs, nwg, [&](uint32_t k) { return desc[order[k]].counter; }, [&](uint32_t k) { return order[k]; },
-        opened.data(), verd.data(), status,
-        [&](uint32_t g, auto&& fn) {
-            std::lock_guard<std::mutex> lk(windows[g]->mu);
-            fn(windows[g]->core);
-        },
+        window_runs(G, nwindows), nwg, [&](uint32_t k) { return desc[G.order[k]].counter; },
+        [&](uint32_t k) { return G.order[k]; }, opened.data(), verd.data(), status, with_window,
         [&](const std::vector<uint32_t>& pk) -> int {
             std::vector<neb_desc> ds(pk.size());
-            std::vector<int32_t> st(pk.size(), NEB_STATUS_BAD_KEY);
             for (size_t j = 0; j < pk.size(); j++) ds[j] = desc[pk[j]];
-            const int r = neb_open_batch_host(e, alg, ds.data(), (uint32_t)ds.size(), arena, arena_len, st.data(),
-                                              key_hint);
-            if (r != NEB_OK) return r;
-            for (size_t j = 0; j < pk.size(); j++) {
-                opened[pk[j]] = 1;
-                verd[pk[j]] = st[j];
-            }
-            return NEB_OK;
+            return open_extra(pk, ds.data(), arena, arena_len, 1);
         },
         [&](const std::vector<uint32_t>& pk) -> int {
             std::vector<neb_desc> ds(pk.size());
-            size_t total = 0;
-            for (uint32_t i : pk) total += (((size_t)desc[i].aad_len + 15) & ~(size_t)15) + desc[i].len + 16 + 16;
-            spec.assign(total, 0);
+            std::vector<std::array<uint64_t, 3>> copies;
             pt_at.assign(n, 0);
-            size_t off = 0;
-            for (size_t j = 0; j < pk.size(); j++) {
-                const neb_desc& d = desc[pk[j]];
-                neb_desc s2 = d;
-                s2.aad_off = off;
-                std::memcpy(spec.data() + off, arena + d.aad_off, d.aad_len);
-                off += ((size_t)d.aad_len + 15) & ~(size_t)15;
-                s2.src_off = s2.dst_off = off;
-                std::memcpy(spec.data() + off, arena + d.src_off, (size_t)d.len + 16);
-                pt_at[pk[j]] = off;
-                off += (((size_t)d.len + 16) + 15) & ~(size_t)15;
-                ds[j] = s2;
-            }
-            std::vector<int32_t> st(pk.size(), NEB_STATUS_BAD_KEY);
-            const int r = neb_open_batch_host(e, alg, ds.data(), (uint32_t)ds.size(), spec.data(), spec.size(),
-                                              st.data(), key_hint);
-            if (r != NEB_OK) return r;
-            for (size_t j = 0; j < pk.size(); j++) {
-                opened[pk[j]] = 2;
-                verd[pk[j]] = st[j];
-            }
-            return NEB_OK;
+            spec.clear();
+            spec.resize(spec_layout(
+                pk, [&](uint32_t i) -> const neb_desc& { return desc[i]; }, ds.data(), pt_at.data(),
+                [&](uint64_t src, uint64_t dst, uint64_t len) { copies.push_back({src, dst, len}); }));
+            for (const auto& c : copies) std::memcpy(spec.data() + c[1], arena + c[0], c[2]);
+            return open_extra(pk, ds.data(), spec.data(), spec.size(), 2);
         },
-        [&](uint32_t cnt, auto&& fn) { pool.run(cnt, fn); }, &commit, &zero);
+        par, &commit, &zero);
     if (rc != NEB_OK) return rc;
     for (uint32_t i : commit) std::memcpy(arena + desc[i].dst_off, spec.data() + pt_at[i], desc[i].len);
     for (uint32_t i : zero) std::memset(arena + desc[i].dst_off, 0, desc[i].len);
-    if (prof)
+    if (RxProf::on())
         std::fprintf(stderr,
-                     "rx n=%u threads %u/%u plan %.1f us (validate %.1f group %.1f split %.1f sim %.1f) stage+gpu %.1f "
+                     "rx n=%u threads 1/%u plan %.1f us (validate %.1f group %.1f split %.1f sim %.1f) stage+gpu %.1f "
                      "(submit->done %.1f) real %.1f us\n",
-                     n, nr, nwg, us(t0, t1), us(t0, ta), us(ta, tb), us(tb, tc), us(tc, t1), us(t1, t2), us(ts, td),
-                     us(t2, now()));
+                     n, nwg, RxProf::us(t0, t1), RxProf::us(t0, ta), RxProf::us(ta, tb), RxProf::us(tb, tc),
+                     RxProf::us(tc, t1), RxProf::us(t1, t2), RxProf::us(ts, td), RxProf::us(t2, now()));
     return NEB_OK;
 }
 
@@ -577,8 +476,8 @@ static int rx_host_finish(neb_engine* e, int alg, neb_dwindows* d, const neb_des
             RX_HIP(hipMemcpyAsync(ws.sub_map, pk.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, s));
             RX_HIP(hipMemcpyAsync(ws.nsub, &cnt, 4, hipMemcpyHostToDevice, s));
             RX_HIP(neb_rxdev_gather(d_desc, cnt, &ws, s));
-            const int r =
-                neb_open_batch_count(e, alg, ws.sub_desc, cnt, nullptr, d_arena, ws.sub_status, key_hint, s, nullptr, nullptr);
+            const int r = neb_launch(e, {.alg = alg, .open = 1, .desc = ws.sub_desc, .n = cnt, .arena = d_arena,
+                                         .status = ws.sub_status, .key_hint = key_hint, .stream = s});
             if (r != NEB_OK) return r;
             std::vector<int32_t> st(cnt);
             RX_HIP(hipMemcpyAsync(st.data(), ws.sub_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
@@ -594,21 +493,11 @@ static int rx_host_finish(neb_engine* e, int alg, neb_dwindows* d, const neb_des
             std::vector<neb_span> sp;
             std::vector<neb_desc> ds(cnt);
             pt_at.assign(n, 0);
-            uint64_t off = 0;
-            for (uint32_t j = 0; j < cnt; j++) {
-                const neb_desc& dd = h_desc[pk[j]];
-                neb_desc s2 = dd;
-                s2.aad_off = off;
-                sp.push_back({dd.aad_off, off, dd.aad_len, 0});
-                off += ((uint64_t)dd.aad_len + 15) & ~15ull;
-                s2.src_off = s2.dst_off = off;
-                sp.push_back({dd.src_off, off, dd.len + 16u, 0});
-                pt_at[pk[j]] = off;
-                off += ((uint64_t)dd.len + 16 + 15) & ~15ull;
-                ds[j] = s2;
-            }
+            const uint64_t bytes = spec_layout(
+                pk, [&](uint32_t i) -> const neb_desc& { return h_desc[i]; }, ds.data(), pt_at.data(),
+                [&](uint64_t src, uint64_t dst, uint64_t len) { sp.push_back({src, dst, (uint32_t)len, 0}); });
             d_spec.reset();  // (every round ends with s synchronized)
-            RX_HIP(d_spec.reserve(off + 16));
+            RX_HIP(d_spec.reserve(bytes));
             int r = run_spans(d_arena, d_spec, sp);
             if (r != NEB_OK) return r;
             neb::DevBuf<neb_desc> d_ds;
@@ -617,8 +506,9 @@ static int rx_host_finish(neb_engine* e, int alg, neb_dwindows* d, const neb_des
             RX_HIP(d_st.reserve((size_t)cnt * 4));
             std::vector<int32_t> st(cnt, NEB_STATUS_BAD_KEY);
             hipError_t err = hipMemcpyAsync(d_ds, ds.data(), (size_t)cnt * sizeof(neb_desc), hipMemcpyHostToDevice, s);
-            r = err == hipSuccess ? neb_open_batch_count(e, alg, d_ds, cnt, nullptr, d_spec, d_st, key_hint, s, nullptr, nullptr)
-                                  : NEB_ERR_HIP;
+            r = err != hipSuccess ? NEB_ERR_HIP
+                                  : neb_launch(e, {.alg = alg, .open = 1, .desc = d_ds, .n = cnt, .arena = d_spec,
+                                                   .status = d_st, .key_hint = key_hint, .stream = s});
             if (r == NEB_OK && (hipMemcpyAsync(st.data(), d_st, (size_t)cnt * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
                                 hipStreamSynchronize(s) != hipSuccess))
                 r = NEB_ERR_HIP;
@@ -681,9 +571,8 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
     d->ws.spin_limit = d->spin_limit;
     const neb::RxDevWs& ws = d->ws;
 
-    static const bool prof = std::getenv("NEB_RX_PROF") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const auto now = RxProf::now;
+    const auto us = RxProf::us;
     const auto t0 = now();
     // Everything is queued at once, one host read at the end: windows whose counters come within
     // 2^62 of wrapping hold all their packets back (admitted by none), and exact_rounds opens what
@@ -708,14 +597,16 @@ static int rx_open_batch_locked(neb_engine* e, int alg, neb_dwindows* d, const n
     const auto t1 = now();
     // 2. one open over the batch that runs the admitted packets only (the plan's mask), writing their
     //    statuses at their arrival indices
-    rc = neb_open_batch_count(e, alg, d_desc, n, nullptr, d_arena, d_status, key_hint, s, ws.adm, prebinned);
+    rc = neb_launch(e, {.alg = alg, .open = 1, .desc = d_desc, .n = n, .arena = d_arena, .status = d_status,
+                        .key_hint = key_hint, .stream = s, .sched = prebinned, .prebinned = prebinned != nullptr,
+                        .rx = ws.adm});
     if (rc != NEB_OK) return rc;
     const auto t2 = now();
     // 3. the verdicts into the windows, and the parallel finish of every window whose packets all verified
     RX_HIP(neb_rxdev_finish(n, &v, &ws, d_status, s));
     const auto t3 = now();
     RX_HIP(hipStreamSynchronize(s));
-    if (prof)
+    if (RxProf::on())
         std::fprintf(stderr, "rxdev n=%u enqueue plan %.1f, open %.1f, finish %.1f us, wait %.1f us\n", n, us(t0, t1),
                      us(t1, t2), us(t2, t3), us(t3, now()));
     // the plan and the open flag, in pinned host memory, whether any window needs the sequential finish
@@ -733,8 +624,7 @@ static int rx_open_wire_host(neb_engine* e, int alg, neb_window* const* windows,
                              uint32_t key_hint, bool relayed) {
     if (!e || (n && (!pk || !arena || !status || !windows))) return NEB_ERR_INVALID;
     if (n == 0) return NEB_OK;
-    for (uint32_t i = 0; i < n; i++)  // every wire packet inside the arena (sums cannot wrap)
-        if (pk[i].off > arena_len || neb_rx_len(pk[i]) > arena_len - pk[i].off) return NEB_ERR_INVALID;
+    if (!wire_in_arena(pk, n, arena_len)) return NEB_ERR_INVALID;
     std::vector<neb_desc> desc(n);
     std::vector<int32_t> gate(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -886,7 +776,8 @@ NEB_API int neb_relay_forward_batch(neb_engine* e, int alg, neb_dwindows* d, con
     const neb::RelayWs& ws = d->relay_ws;
     RX_HIP(neb_relay_plan(d_pk, d_route, d_status, n, d_tunnels, ntunnels, d_keys, max_keys, alg, d_arena, d_fwd_status,
                           &ws, s));
-    rc = neb_seal_batch_count(e, alg, ws.sub_desc, n, ws.nsub, d_arena, ws.sub_status, seal_hint, s);
+    rc = neb_launch(e, {.alg = alg, .open = 0, .desc = ws.sub_desc, .n = n, .d_n = ws.nsub, .arena = d_arena,
+                        .status = ws.sub_status, .key_hint = seal_hint, .stream = s, .note_use = true});
     if (rc == NEB_OK && neb_relay_fix(&ws, n, d_fwd_status, s) != hipSuccess) rc = NEB_ERR_HIP;
     (void)d->relay.end(s);
     return rc;
@@ -940,8 +831,7 @@ NEB_API int neb_rx_via_unwrap_host(const neb_rx_packet* pk, const neb_rx_via* vi
                                    const uint8_t* arena, size_t arena_len, neb_rx_packet* inner_pk,
                                    int32_t* inner_status) {
     if (n && (!pk || !via || !status || !arena || !inner_pk || !inner_status)) return NEB_ERR_INVALID;
-    for (uint32_t i = 0; i < n; i++)
-        if (pk[i].off > arena_len || neb_rx_len(pk[i]) > arena_len - pk[i].off) return NEB_ERR_INVALID;
+    if (!wire_in_arena(pk, n, arena_len)) return NEB_ERR_INVALID;
     for (uint32_t i = 0; i < n; i++) {
         const bool ok = status[i] == NEB_STATUS_OK && neb_rx_len(pk[i]) >= 2u;
         const uint8_t* h = arena + pk[i].off;
