@@ -268,6 +268,25 @@ def stage(packets):
     return plain, np.frombuffer(b"\xA5" * 3 + b"".join(parts) + b"\x5A" * 16, np.uint8).copy()
 
 
+STAGE_LEAD = 3  # the filler in front of the first record, as in stage
+
+
+def stage_padded(packets, pads=None):
+    """stage with pads[i] filler bytes in front of record i (default: the packet's own "pad", or
+    none), so a record's source offset can fall at a chosen residue mod 16. Without pads: stage."""
+    if pads is None:
+        pads = [p.get("pad", 0) for p in packets]
+    plain = np.zeros(len(packets), L.PLAIN_PACKET_DTYPE)
+    parts, off = [b"\xA5" * STAGE_LEAD], STAGE_LEAD
+    for i, (p, pad) in enumerate(zip(packets, pads)):
+        d = p["data"]
+        off += pad
+        plain[i] = (off, p["epoch"], p["counter"], len(d), p.get("ip_hdr_len", 0), p.get("proto", 0), p.get("flags", 0))
+        parts += [b"\x3C" * pad, d]
+        off += len(d)
+    return plain, np.frombuffer(b"".join(parts) + b"\x5A" * 16, np.uint8).copy()
+
+
 def default_cap(packets):
     return sum(M.align16(len(p["data"])) for p in packets)
 

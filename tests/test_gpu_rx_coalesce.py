@@ -17,17 +17,25 @@ pytestmark = pytest.mark.gpu
 CANARY = 0xC7
 
 
-def run_device(engine, packets, lanes=K.BOTH, out_cap=None, max_writes=None):
+def run_device(engine, packets, lanes=K.BOTH, out_cap=None, max_writes=None, stage=K.stage, shift=(0, 0)):
+    """stage: how the packets are laid out in the input arena. shift: d_in and d_out are views that
+    start this many bytes off a 16-byte boundary (out_off stays a 16-aligned offset into d_out)."""
     import torch
 
     dev = torch.device("cuda", engine.device)
-    plain, arena = K.stage(packets)
+    plain, arena = stage(packets)
     n = len(packets)
     cap = K.default_cap(packets) if out_cap is None else out_cap
     mw = n if max_writes is None else max_writes
     up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
-    d_plain, d_in = up(plain), up(arena)
-    d_out = torch.full((cap + 64,), CANARY, dtype=torch.uint8, device=dev)
+    d_plain = up(plain)
+    in_buf = torch.zeros(shift[0] + arena.size, dtype=torch.uint8, device=dev)
+    d_in = in_buf[shift[0]:]
+    d_in.copy_(up(arena))
+    front = 64 + shift[1]
+    out_buf = torch.full((front + cap + 64,), CANARY, dtype=torch.uint8, device=dev)
+    d_out = out_buf[front:]
+    assert (d_in.data_ptr() % 16, d_out.data_ptr() % 16) == shift
     d_writes = torch.zeros((mw + 1) * L.TUN_WRITE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
     d_nw = torch.full((1,), -5, dtype=torch.int32, device=dev)
     d_pw = torch.full((n,), -7, dtype=torch.int32, device=dev)
@@ -39,6 +47,7 @@ def run_device(engine, packets, lanes=K.BOTH, out_cap=None, max_writes=None):
     torch.cuda.synchronize(dev)
     out = d_out.cpu().numpy()
     assert (out[cap:] == CANARY).all(), "wrote past out_cap"
+    assert (out_buf[:front].cpu().numpy() == CANARY).all(), "wrote in front of the output arena"
     assert (d_in.cpu().numpy() == arena).all(), "the input arena is read-only"
     nw = int(d_nw.item())
     assert 0 <= nw <= mw
