@@ -1465,7 +1465,7 @@ static int tx_run(neb_engine* e, int alg, neb_tx_tunnel* d_tun, uint32_t ntun, c
     HIP_TRY(neb_tx_plan(d_pk, npk, d_in, d_tun, ntun, d_via, e->d_keys, e->max_keys, alg, &tx.ws, out_cap, max_wires,
                         d_pk_status, d_nwires, s));
     // one tunnel key with AES-GCM: the seal sums the payload into the L4 checksums itself, so the
-    // segment kernel does not read the payload (aes_gcm.hip gcm_csum_fix)
+    // segment kernel does not read the payload (gcm_packet.hpp gcm_csum_fix)
     const bool cs = alg == NEB_ALG_AESGCM && key_hint != NEB_KEYS_MIXED;
     const uint32_t cs_slots = cs ? neb_gcm_single_slots(max_wires, e->cu_count, 0, 2) : 0u;
     HIP_TRY(neb_tx_segment(d_pk, npk, d_in, d_tun, d_via, d_out, &tx.ws, d_wires, d_nwires, max_wires, e->cu_count,

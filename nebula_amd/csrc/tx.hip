@@ -640,7 +640,7 @@ constexpr int kTxWaves = 4;
 #define NEB_TX_MINBLOCKS 4
 #endif
 constexpr uint32_t kTxGroup = NEB_TX_GROUP;        // lanes per segment: 64 / kTxGroup segments per wave
-// the longest plaintext prefix a seal descriptor's flags can name beside a checksum field (aes_gcm.hip kCsHdrMask)
+// the longest plaintext prefix a seal descriptor's flags can name beside a checksum field (gcm_packet.hpp kCsHdrMask)
 constexpr uint32_t kTxMaxPrefix = 0xFFFu;
 constexpr uint32_t kTxRegUnits = NEB_TX_REGUNITS;  // payload units per lane kept in registers (16 x 6 x 16 B = 1.5 KiB)
 
@@ -670,7 +670,7 @@ __global__ __launch_bounds__(kTxWaves * 64, CSM ? NEB_TX_CSM_BLOCKS : NEB_TX_MIN
                                                                      uint32_t cs_slots) {
     const uint32_t g = threadIdx.x & (kTxGroup - 1u);  // lane within the segment's group
     const uint32_t nw = __builtin_amdgcn_readfirstlane(*d_nwires);
-    // cs_slots != 0: the single-key seal sums the payload into the L4 checksums (aes_gcm.hip
+    // cs_slots != 0: the single-key seal sums the payload into the L4 checksums (gcm_packet.hpp
     // gcm_csum_fix), except for the segments after its last full pass of cs_slots waves x 16
     // packets, which its tail kernel seals: those are summed here
     const uint32_t ngroups = (nw + 15u) / 16u;

@@ -1,5 +1,5 @@
-"""CPU model of the key-setup kernel's GF(2^128) word arithmetic (aes_gcm.hip): gf_mul_xpow (q·x^i as
-a shifted 256-bit product, reduced by gf_reduce) builds every basis table of gcm_key_setup_kernel in
+"""CPU model of the key-setup kernel's GF(2^128) word arithmetic (gf128.hpp): gf_mul_xpow (q·x^i as a
+shifted 256-bit product, reduced by gf_reduce) builds every basis table of gcm_key_setup_kernel in
 parallel, one lane per power. The model follows the device code word for word and is checked
 against the bit-serial multiply by x (gf_mulx) it replaced, for every i < 128."""
 import random
@@ -58,9 +58,10 @@ def _gmul(a, b):
 
 
 def _ghash_lanes(X, H, lpp, U):
-    """The GHASH pass's lane layout (aes_gcm.hip ghash_packet_group): the n blocks front-padded to
-    lpp·R, lane l owning padded blocks lpp·r + l; rounds aggregated U at a time (zero rounds in
-    front), A <- A·H^(U·lpp) ⊕ Σ_i X_i·H^((U-1-i)·lpp); then Σ_l A_l·H^(lpp-l)."""
+    """The packet group's GHASH lane layout (gcm_packet.hpp gcm_packet_group): the n blocks
+    front-padded to lpp·R, lane l owning padded blocks lpp·r + l; rounds aggregated U at a time (zero
+    rounds in front; the kernels run U = 1), A <- A·H^(U·lpp) ⊕ Σ_i X_i·H^((U-1-i)·lpp); then
+    Σ_l A_l·H^(lpp-l)."""
     n = len(X)
     R = -(-n // lpp)
     pad = lpp * R - n

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY: directed TUN reads for the transmit path (nebula_amd/csrc/tx.hip
-tx_parse_one and tx_segment_kernel; the seal-side checksum of nebula_amd/csrc/aes_gcm.hip
+tx_parse_one and tx_segment_kernel; the seal-side checksum of nebula_amd/csrc/gcm_packet.hpp
 gcm_csum_fix), for tests/test_tx_cases.py (CPU) and tests/test_gpu_tx_edges.py (GPU).
 
 Header builders with every field the kernels branch or do arithmetic on as a parameter, payload
