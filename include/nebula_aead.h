@@ -53,6 +53,9 @@
  *                            QueryRelayIndex (outside.go:93-106, hostmap.go:546-577) and
  *                            handleOutsideRelayPacket's QueryRelayForByIdx / QueryVpnAddrsRelayFor
  *                            (outside.go:201-240), over neb_index_table_*
+ *   neb_rx_inner_batch       handleOutsideMessagePacket between Decrypt and Commit (outside.go:474-494):
+ *                            newPacket(out, true, fp) and the two address checks at the head of
+ *                            firewall.Drop (firewall.go:425-457), over neb_peer_table_*
  *   neb_queue_*              the flush points themselves (flushSendBatch interface.go:478-487,
  *                            listenOut's flush :395-400) of every routine (interface.go:320-335),
  *                            gathered into shared device batches
@@ -883,6 +886,92 @@ NEB_API int neb_tx_resolve_batch(neb_engine* e, const neb_tx_table* t, neb_tx_pa
  * against in_len first (NEB_ERR_INVALID: nothing written). */
 NEB_API int neb_tx_resolve_batch_host(const neb_tx_table* t, neb_tx_packet* packets, uint32_t npackets,
                                       const uint8_t* in, size_t in_len, neb_fw_packet* fw, int32_t* status);
+/* ---- RX inner resolve: parse opened packets, check the peer's and the own addresses ------------- */
+/* What handleOutsideMessagePacket does between Decrypt and Commit (outside.go:474-494) short of the
+ * rules and conntrack: newPacket(out, true, fwPacket) and the first two checks of firewall.Drop
+ * (firewall.go:425-457): the inner source address must belong to the peer's certificate
+ * (h.networks.Lookup(fp.RemoteAddr), hostmap.go:837-857) and the inner destination to our routable
+ * networks (routableNetworks.Contains(fp.LocalAddr), firewall.go:154-165). Both are pure functions of
+ * the packet's first bytes over state that changes only at handshakes and config reloads, so the state
+ * lives in a table beside the keys, and one call takes neb_rx_plain_from_wire's place between
+ * neb_rx_open_wire_batch / neb_rx_open_via_batch and neb_rx_coalesce_batch. */
+#define NEB_STATUS_RX_BAD_REMOTE 13    /* ErrInvalidRemoteIP */
+#define NEB_STATUS_RX_PEER_REJECTED 14 /* ErrPeerRejected */
+#define NEB_STATUS_RX_BAD_LOCAL 15     /* ErrInvalidLocalIP */
+#define NEB_NET_VPN 1      /* NetworkTypeVPN (hostmap.go:228-238) */
+#define NEB_NET_VPN_PEER 2 /* NetworkTypeVPNPeer */
+#define NEB_NET_UNSAFE 3   /* NetworkTypeUnsafe */
+#define NEB_RX_MAX_ROUTABLE 32
+typedef struct neb_peer_net { /* one entry of a HostInfo's networks table */
+    uint32_t tunnel;          /* the packets' key_id: the window / key slot; never NEB_KEYS_MIXED */
+    uint32_t type;            /* NEB_NET_* */
+    neb_cidr prefix;          /* host bits are ignored, as bart's Insert does */
+} neb_peer_net;
+typedef struct neb_peer_key {
+    uint32_t tunnel;
+    neb_cidr prefix;
+} neb_peer_key;
+typedef struct neb_peer_table neb_peer_table;
+
+/* A table of at most `capacity` live entries over all tunnels (fixed; 1..2^20). e == NULL: a
+ * host-only table (neb_rx_inner_batch_host only); otherwise the table also keeps its image in e's
+ * device memory. An entry's key is (tunnel, family, bits, masked prefix). The simple case of
+ * firewall.Drop (h.networks == nil: the remote address must equal h.vpnAddrs[0]) has no form of its
+ * own: it is a tunnel with one full-length NEB_NET_VPN entry. */
+NEB_API int neb_peer_table_create(neb_engine* e, uint32_t capacity, neb_peer_table** out);
+/* No call on the table may be in progress; waits for the device work the table has enqueued. */
+NEB_API int neb_peer_table_destroy(neb_peer_table* t);
+/* A tunnel's entries come with its handshake and go when it closes. The deletions in array order,
+ * then the puts in array order; a put of a live key replaces its type (so puts in buildNetworks'
+ * order give the reference's overwrite when an unsafe network equals a VPN address); deleting an
+ * absent key is not an error. NEB_ERR_INVALID (nothing applied): a type outside 1..3, a bad family
+ * or prefix length, tunnel == NEB_KEYS_MIXED, or the call's bookkeeping could not be allocated.
+ * NEB_ERR_NO_KEY_SLOT (nothing applied): more than `capacity` entries would be live after the call.
+ * Thread-safe. Visibility, ordering and compaction are neb_tx_table_update_hosts': a call enqueued on
+ * `stream` after this one sees the update; one running on another stream meanwhile sees, for every
+ * key, its record from before or from after, and never misses a key that is live before and after;
+ * when deleted and replaced records have filled 3/4 of the slots the call rebuilds the spare image
+ * and blocks until it has switched over. stream is ignored by a host-only table. */
+NEB_API int neb_peer_table_update(neb_peer_table* t, const neb_peer_key* del, uint32_t ndel, const neb_peer_net* put,
+                                  uint32_t nput, void* stream);
+/* Replaces the routable set (firewall.go:154-165): the own VPN addresses at full length and the own
+ * unsafe networks, at most NEB_RX_MAX_ROUTABLE (NEB_ERR_INVALID: more, a bad family or prefix
+ * length). Calls made after this returns use the new set. */
+NEB_API int neb_peer_table_set_routable(neb_peer_table* t, const neb_cidr* nets, uint32_t n);
+NEB_API int neb_peer_table_count(const neb_peer_table* t, uint32_t* live);
+/* For tests, from the host copy: out = {found, slot, probes} as neb_index_table_probe. */
+NEB_API int neb_peer_table_probe(const neb_peer_table* t, const neb_peer_key* key, uint32_t out[3]);
+/* pk / status: a finished neb_rx_open_wire_batch, or the inner_pk / inner_status of
+ * neb_rx_open_via_batch. Per packet i, with len = pk[i].len without NEB_RX_OWN_SOURCE:
+ *   not committed by neb_rx_plain_from_wire's rule (status OK, header Message / None, key_id < nepoch,
+ *   len >= 32): plain[i] as that call writes it (NEB_PLAIN_SKIP), fw[i] zero, inner status
+ *   NEB_STATUS_NOT_MESSAGE;
+ *   newPacket(data, true, fp) over the len - 32 bytes at off + 16 fails: NEB_STATUS_INVALID, plain[i]
+ *   as above, fw[i] zero but for ip_hdr_len and NEB_FW_FRAG_ANY as newPacket had left them;
+ *   otherwise fw[i] is the ParsedPacket, locally oriented (remote = the inner source; the ICMP /
+ *   ICMPv6-echo identifier is remote_port, local_port 0), gateway NEB_GATEWAY_NONE, and
+ *   the longest prefix among tunnel key_id's entries that contains the remote address (netip's
+ *   families: a 4-byte address matches v4 entries only, a 16-byte one, 4-in-6 included, v6 entries
+ *   only): none is NEB_STATUS_RX_BAD_REMOTE, NEB_NET_VPN_PEER is NEB_STATUS_RX_PEER_REJECTED;
+ *   then the routable set does not contain the local address: NEB_STATUS_RX_BAD_LOCAL;
+ *   a refused packet gets NEB_PLAIN_SKIP in plain[i] (fw[i] stays the parse: the caller's
+ *   rejectOutside); a passing one NEB_STATUS_OK and neb_rx_plain_from_wire's record with
+ *   NEB_PLAIN_PARSED, proto, ip_hdr_len and NEB_PLAIN_FRAG_ANY, which neb_rx_coalesce_batch then uses
+ *   instead of deriving them.
+ * Writes plain, fw and inner_status (the last two may be NULL: not written) and nothing else; reads
+ * the 16-byte header and [off + 16, off + len - 16) of a packet and nothing else of the arena.
+ * d_plain and d_fw are 16-byte aligned. n == 0 returns NEB_OK. Only enqueues one kernel on `stream`.
+ * NEB_ERR_INVALID for a host-only table. */
+NEB_API int neb_rx_inner_batch(neb_engine* e, const neb_peer_table* t, const neb_rx_packet* d_pk,
+                               const int32_t* d_status, const uint64_t* d_epoch, uint32_t nepoch, uint32_t n,
+                               const uint8_t* d_arena, neb_plain_packet* d_plain, neb_fw_packet* d_fw,
+                               int32_t* d_inner_status, void* stream);
+/* The same over host memory, from the table's host copy (any table). Every pk is checked against
+ * arena_len first (NEB_ERR_INVALID: nothing written). */
+NEB_API int neb_rx_inner_batch_host(const neb_peer_table* t, const neb_rx_packet* pk, const int32_t* status,
+                                    const uint64_t* epoch, uint32_t nepoch, uint32_t n, const uint8_t* arena,
+                                    size_t arena_len, neb_plain_packet* plain, neb_fw_packet* fw,
+                                    int32_t* inner_status);
 /* ---- submission queue: many threads' small flushes -> device-sized batches -------------------- */
 /* Nebula seals <= 128 packets per TX flush (overlay/batch/tx_batch.go:5, flushSendBatch
  * interface.go:465-487) and opens <= listen.batch = 64 per RX flush (main.go:181, listenOut

@@ -41,6 +41,9 @@ STATUS_NOT_RELAYED = 9  # neb_rx_open_via_batch's inner_status: not a verified t
 STATUS_TX_DROPPED = 10  # neb_tx_resolve_batch: a gate dropped the read (FW_GATE_* says which)
 STATUS_NO_ROUTE = 11  # neb_tx_resolve_batch: not in an own network and no route
 STATUS_NO_TUNNEL = 12  # neb_tx_resolve_batch: no host entry yet, the caller handshakes
+STATUS_RX_BAD_REMOTE = 13  # neb_rx_inner_batch: ErrInvalidRemoteIP
+STATUS_RX_PEER_REJECTED = 14  # neb_rx_inner_batch: ErrPeerRejected
+STATUS_RX_BAD_LOCAL = 15  # neb_rx_inner_batch: ErrInvalidLocalIP
 
 OVERHEAD = 16
 HEADER_LEN = 16
@@ -100,6 +103,15 @@ FW_PACKET_DTYPE = np.dtype([("local_addr", "u1", (16,)), ("remote_addr", "u1", (
                             ("reserved", "u1"), ("ip_hdr_len", "<u2"), ("reserved2", "<u2"), ("gateway", "<u4")])
 assert TX_ADDR_DTYPE.itemsize == 20 and TX_HOST_DTYPE.itemsize == 24
 assert GATEWAY_DTYPE.itemsize == 24 and ROUTE_DTYPE.itemsize == 408 and FW_PACKET_DTYPE.itemsize == 48
+
+# neb_peer_table_* (include/nebula_aead.h): every tunnel's certificate networks, the routable set
+NET_VPN, NET_VPN_PEER, NET_UNSAFE = 1, 2, 3
+RX_MAX_ROUTABLE = 32
+PEER_NET_DTYPE = np.dtype([("tunnel", "<u4"), ("type", "<u4"), ("addr", "u1", (16,)), ("family", "u1"), ("bits", "u1"),
+                           ("reserved", "u1", (2,))])
+PEER_KEY_DTYPE = np.dtype([("tunnel", "<u4"), ("addr", "u1", (16,)), ("family", "u1"), ("bits", "u1"),
+                           ("reserved", "u1", (2,))])
+assert PEER_NET_DTYPE.itemsize == 28 and PEER_KEY_DTYPE.itemsize == 24
 
 # neb_plain_packet (include/nebula_aead.h): one MultiCoalescer.Commit
 PLAIN_PARSED, PLAIN_FRAG_ANY, PLAIN_SKIP = 1, 2, 4
@@ -198,6 +210,14 @@ SIGNATURES = {
     "neb_tx_table_probe": (_i, [_vp, _u32, _vp, C.POINTER(_u32)]),
     "neb_tx_resolve_batch": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "neb_tx_resolve_batch_host": (_i, [_vp, _vp, _u32, _vp, _sz, _vp, _vp]),
+    "neb_peer_table_create": (_i, [_vp, _u32, C.POINTER(_vp)]),
+    "neb_peer_table_destroy": (_i, [_vp]),
+    "neb_peer_table_update": (_i, [_vp, _vp, _u32, _vp, _u32, _vp]),
+    "neb_peer_table_set_routable": (_i, [_vp, _vp, _u32]),
+    "neb_peer_table_count": (_i, [_vp, C.POINTER(_u32)]),
+    "neb_peer_table_probe": (_i, [_vp, _vp, C.POINTER(_u32)]),
+    "neb_rx_inner_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "neb_rx_inner_batch_host": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp, _vp, _vp]),
     "neb_seal_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_open_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_seal_batch_sharded": (_i, [_i, _vp, _u32, _u32]),

@@ -138,7 +138,25 @@ __device__ __forceinline__ void one_publish_status(int32_t* host_status, const i
     if (__lane_id() == 0) __hip_atomic_store(host_status, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// A word of a lookup table's device image (resolve.hip, route.hip): an 8-byte agent-scope atomic
+// The bytes [p, p + len) of an arena, p of any alignment (route.hip, peer.hip): byte k comes out of
+// the aligned dword around it where that dword lies inside the span, else from a byte load, so
+// nothing outside the span is read. Called for k < len only.
+struct SpanBytes {
+    const uint8_t* h;
+    const uint32_t* dw;
+    uint32_t sh;
+    uint64_t end;
+    __device__ __forceinline__ SpanBytes(const uint8_t* p, uint32_t len)
+        : h(p), dw(reinterpret_cast<const uint32_t*>(p - (reinterpret_cast<uintptr_t>(p) & 3u))),
+          sh((uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u)), end((uint64_t)(reinterpret_cast<uintptr_t>(p) & 3u) + len) {}
+    __device__ __forceinline__ uint32_t operator()(uint32_t k) const {
+        const uint32_t j = k + sh, at = j & ~3u;
+        if (at >= sh && (uint64_t)at + 4u <= end) return (dw[j >> 2] >> (8u * (j & 3u))) & 255u;
+        return h[k];
+    }
+};
+
+// A word of a lookup table's device image (resolve.hip, route.hip, peer.hip): an 8-byte agent-scope atomic
 // load, served by the L2 and never by a CU's L1.
 struct LoadAgent {
     __device__ __forceinline__ uint64_t operator()(const uint64_t* p) const {

@@ -298,8 +298,7 @@ extern "C" NEB_API int neb_tx_table_set_routes(neb_tx_table* t, const neb_route*
             gws.push_back(TxGw{tx_addr_from_bytes(r.gateways[k].addr.addr, r.gateways[k].addr.family), r.gateways[k].addr.family,
                                total ? tx_bucket_bound(upto, total) : 0x7FFFFFFFu});
         }
-        if (rec.family == 4) lens.v4 |= 1ull << rec.bits;
-        else lens.v6[rec.bits >> 6] |= 1ull << (rec.bits & 63u);
+        tx_lens_add(&lens, rec.family, rec.bits);
     }
     if (recs.size() > t->route_cap || gws.size() > t->gw_cap) return NEB_ERR_NO_KEY_SLOT;
     std::unique_lock<std::shared_mutex> g(t->mu);

@@ -43,18 +43,9 @@ __global__ __launch_bounds__(256) void tx_resolve_kernel(TxResolveArgs a) {
     const uint64_t in_off = a.pk[i].in_off;
     const uint32_t len = a.pk[i].len;
 
-    // in_off has no alignment (a virtio header in front leaves it at 2 mod 4): a byte comes out of
-    // the aligned dword around it where that dword lies inside the packet, else from a byte load,
-    // so nothing outside [in_off, in_off + len) is read
-    const uint8_t* h = a.in + in_off;
-    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(h) & 3u);
-    const uint32_t* dw = reinterpret_cast<const uint32_t*>(h - sh);
-    const uint64_t end = (uint64_t)sh + len;
-    auto byte = [&](uint32_t k) -> uint32_t {
-        const uint32_t j = k + sh, at = j & ~3u;
-        if (at >= sh && (uint64_t)at + 4u <= end) return (dw[j >> 2] >> (8u * (j & 3u))) & 255u;
-        return h[k];
-    };
+    // in_off has no alignment (a virtio header in front leaves it at 2 mod 4): nothing outside
+    // [in_off, in_off + len) is read
+    const SpanBytes byte(a.in + in_off, len);
     auto look = [&](uint32_t kind, uint32_t family, uint32_t bits, const TxAddr& addr, uint64_t* v) {
         return tx_lookup(a.image, a.mask, kind, family, bits, addr, LoadAgent{}, v);
     };

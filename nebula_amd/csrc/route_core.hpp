@@ -3,7 +3,7 @@
 // (tests/sanitize_route). Plain C++17; compiles with g++ alone (no HIP headers).
 //
 // Restated from slackhq/nebula (read as text, not copied):
-//   newPacket / parseV4 / parseV6          outside.go:320-472 (incoming == false)
+//   newPacket / parseV4 / parseV6          outside.go:320-472 (incoming == false; == true for peer_core.hpp)
 //   IPv6FindUpperProtocol                  iputil/packet.go:349-395
 //   the broadcast, self, multicast gates   inside.go:43-76, pki.go:475-487
 //   getOrHandshakeConsiderRouting          inside.go:292-372
@@ -98,13 +98,17 @@ inline void tx_own_set(TxOwn* o, const neb_cidr* nets, uint32_t n, uint32_t flag
     }
 }
 
-NEB_RT_HD uint64_t tx_hash(uint32_t kind, uint32_t family, uint32_t bits, const TxAddr& a) {
-    uint64_t x = a.hi ^ (a.lo * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)((kind << 16) | (family << 8) | bits) * 0xD6E8FEB86659FD93ull);
+// The hash of an address and 64 bits of whatever else the key holds (also peer_core.hpp).
+NEB_RT_HD uint64_t tx_mix(const TxAddr& a, uint64_t rest) {
+    uint64_t x = a.hi ^ (a.lo * 0x9E3779B97F4A7C15ull) ^ (rest * 0xD6E8FEB86659FD93ull);
     x ^= x >> 32;
     x *= 0xD6E8FEB86659FD93ull;
     x ^= x >> 32;
     x *= 0xD6E8FEB86659FD93ull;
     return x ^ (x >> 32);
+}
+NEB_RT_HD uint64_t tx_hash(uint32_t kind, uint32_t family, uint32_t bits, const TxAddr& a) {
+    return tx_mix(a, (kind << 16) | (family << 8) | bits);
 }
 NEB_RT_HD uint64_t tx_tag(uint32_t kind, uint32_t family, uint32_t bits, uint64_t hash) {
     return (1ull << 63) | ((uint64_t)kind << 62) | ((uint64_t)(family == 6) << 61) | ((uint64_t)bits << 48) | (hash >> 16);
@@ -115,13 +119,13 @@ NEB_RT_HD uint32_t tx_slots_for(uint32_t entries) {  // entries <= 2^28
     return s;
 }
 
-// The search for (kind, family, bits, a): walks the chain from the key's home slot to the key or to
-// the first EMPTY slot. ld(p) reads one 64-bit word of the image. Reads a slot's words in program
-// order: tag, then the address words. *slot: where it ended; *probes: slots examined.
+// The search for the record with tag `want` and address a whose hash is h: walks the chain from the
+// key's home slot to the key or to the first EMPTY slot. ld(p) reads one 64-bit word of the image.
+// Reads a slot's words in program order: tag, then the address words. *slot: where it ended;
+// *probes: slots examined.
 template <class Load>
-NEB_RT_HD bool tx_find(const TxSlot* slots, uint32_t mask, uint32_t kind, uint32_t family, uint32_t bits,
-                       const TxAddr& a, Load ld, uint32_t* slot, uint32_t* probes) {
-    const uint64_t h = tx_hash(kind, family, bits, a), want = tx_tag(kind, family, bits, h);
+NEB_RT_HD bool tx_find_tag(const TxSlot* slots, uint32_t mask, uint64_t h, uint64_t want, const TxAddr& a, Load ld,
+                           uint32_t* slot, uint32_t* probes) {
     uint32_t s = (uint32_t)h & mask;
     for (uint32_t k = 1; k <= mask + 1u; k++, s = (s + 1u) & mask) {
         const uint64_t t = ld(&slots[s].tag);
@@ -140,6 +144,13 @@ NEB_RT_HD bool tx_find(const TxSlot* slots, uint32_t mask, uint32_t kind, uint32
     *probes = mask + 1u;
     return false;
 }
+// The search for (kind, family, bits, a).
+template <class Load>
+NEB_RT_HD bool tx_find(const TxSlot* slots, uint32_t mask, uint32_t kind, uint32_t family, uint32_t bits,
+                       const TxAddr& a, Load ld, uint32_t* slot, uint32_t* probes) {
+    const uint64_t h = tx_hash(kind, family, bits, a);
+    return tx_find_tag(slots, mask, h, tx_tag(kind, family, bits, h), a, ld, slot, probes);
+}
 template <class Load>
 NEB_RT_HD bool tx_lookup(const TxSlot* slots, uint32_t mask, uint32_t kind, uint32_t family, uint32_t bits,
                          const TxAddr& a, Load ld, uint64_t* value) {
@@ -149,7 +160,7 @@ NEB_RT_HD bool tx_lookup(const TxSlot* slots, uint32_t mask, uint32_t kind, uint
     return true;
 }
 
-// ---- newPacket(data, false, fp) -------------------------------------------------------------------
+// ---- newPacket(data, incoming, fp) ----------------------------------------------------------------
 
 struct TxParsed {
     TxAddr local, remote;
@@ -160,8 +171,10 @@ struct TxParsed {
 };
 
 // byte(i): byte i of the packet, called for i < len only. false: newPacket's error; ip_hdr_len and
-// NEB_FW_FRAG_ANY are then as newPacket had left them and every other field is zero.
-template <class Byte>
+// NEB_FW_FRAG_ANY are then as newPacket had left them and every other field is zero. kIncoming: the
+// record is locally oriented, so the source is the remote side, for addresses and ports; the ICMP /
+// ICMPv6-echo identifier is remote_port either way (outside.go:345-351, 378-399, 449-469).
+template <bool kIncoming = false, class Byte>
 NEB_RT_HD bool tx_new_packet(uint32_t len, Byte byte, TxParsed* p) {
     auto be16 = [&](uint32_t i) { return (byte(i) << 8) | byte(i + 1u); };
     auto be32 = [&](uint32_t i) { return ((uint64_t)be16(i) << 16) | be16(i + 2u); };
@@ -182,15 +195,15 @@ NEB_RT_HD bool tx_new_packet(uint32_t len, Byte byte, TxParsed* p) {
         if (len < ihl + (fragment ? 0u : proto == 1u ? 6u : 4u)) return false;
         p->protocol = proto;
         p->family = 4u;
-        p->local = TxAddr{be32(12u) << 32, 0};
-        p->remote = TxAddr{be32(16u) << 32, 0};
+        p->local = TxAddr{be32(kIncoming ? 16u : 12u) << 32, 0};
+        p->remote = TxAddr{be32(kIncoming ? 12u : 16u) << 32, 0};
         if (fragment) {
             p->flags |= NEB_FW_FRAGMENT;
         } else if (proto == 1u) {
             p->remote_port = be16(ihl + 4u);
         } else {
-            p->local_port = be16(ihl);
-            p->remote_port = be16(ihl + 2u);
+            p->local_port = be16(ihl + (kIncoming ? 2u : 0u));
+            p->remote_port = be16(ihl + (kIncoming ? 0u : 2u));
         }
         return true;
     }
@@ -235,16 +248,16 @@ NEB_RT_HD bool tx_new_packet(uint32_t len, Byte byte, TxParsed* p) {
             }
         } else if (nh == 6u || nh == 17u) {
             if (len < off + 4u) return false;
-            p->local_port = be16(off);
-            p->remote_port = be16(off + 2u);
+            p->local_port = be16(off + (kIncoming ? 2u : 0u));
+            p->remote_port = be16(off + (kIncoming ? 0u : 2u));
         }
     } else {
         p->flags |= NEB_FW_FRAGMENT;
     }
     p->protocol = nh;
     p->family = 6u;
-    p->local = TxAddr{be64(8u), be64(16u)};
-    p->remote = TxAddr{be64(24u), be64(32u)};
+    p->local = TxAddr{be64(kIncoming ? 24u : 8u), be64(kIncoming ? 32u : 16u)};
+    p->remote = TxAddr{be64(kIncoming ? 8u : 24u), be64(kIncoming ? 16u : 32u)};
     return true;
 }
 
@@ -289,6 +302,35 @@ inline uint32_t tx_bucket_bound(uint64_t upto, uint64_t total) {  // total > 0, 
     return (uint32_t)(((upto << 31) + total / 2) / total) - 1u;
 }
 
+// ---- longest prefix -------------------------------------------------------------------------------
+
+// RoutesFor's method (also peer_core.hpp): one probe per prefix length present, the longest first.
+// probe(bits, masked address) -> found.
+template <class Probe>
+NEB_RT_HD bool tx_longest_prefix(const TxLens& lens, uint32_t family, const TxAddr& a, Probe probe) {
+    bool found = false;
+    auto scan = [&](uint64_t m, uint32_t base) {  // the lengths base + 63 .. base that are present
+        while (m && !found) {
+            const uint32_t b = 63u - (uint32_t)__builtin_clzll(m);
+            m &= ~(1ull << b);
+            const TxAddr pm = tx_prefix_mask(base + b);
+            found = probe(base + b, TxAddr{a.hi & pm.hi, a.lo & pm.lo});
+        }
+    };
+    if (family == 4u) {
+        scan(lens.v4, 0u);
+    } else {
+        scan(lens.v6[2], 128u);
+        scan(lens.v6[1], 64u);
+        scan(lens.v6[0], 0u);
+    }
+    return found;
+}
+inline void tx_lens_add(TxLens* l, uint32_t family, uint32_t bits) {
+    if (family == 4) l->v4 |= 1ull << bits;
+    else l->v6[bits >> 6] |= 1ull << (bits & 63u);
+}
+
 // ---- the resolve of one TUN read ------------------------------------------------------------------
 
 struct TxResult {
@@ -328,23 +370,9 @@ NEB_RT_HD void tx_resolve_one(uint32_t len, Byte byte, const TxOwn& own, const T
         if (look((uint32_t)NEB_TX_KIND_HOST, p.family, 0u, p.remote, &v)) out->tunnel = (uint32_t)v;
         else status = NEB_STATUS_NO_TUNNEL;
     } else {
-        // RoutesFor: one probe per prefix length present, the longest first
-        bool found = false;
-        auto scan = [&](uint64_t m, uint32_t base) {  // the lengths base + 63 .. base that are present
-            while (m && !found) {
-                const uint32_t b = 63u - (uint32_t)__builtin_clzll(m);
-                m &= ~(1ull << b);
-                const TxAddr pm = tx_prefix_mask(base + b);
-                found = look((uint32_t)NEB_TX_KIND_ROUTE, p.family, base + b, TxAddr{p.remote.hi & pm.hi, p.remote.lo & pm.lo}, &v);
-            }
-        };
-        if (p.family == 4u) {
-            scan(lens.v4, 0u);
-        } else {
-            scan(lens.v6[2], 128u);
-            scan(lens.v6[1], 64u);
-            scan(lens.v6[0], 0u);
-        }
+        const bool found = tx_longest_prefix(lens, p.family, p.remote, [&](uint32_t bits, const TxAddr& masked) {
+            return look((uint32_t)NEB_TX_KIND_ROUTE, p.family, bits, masked, &v);
+        });
         if (!found) {
             status = NEB_STATUS_NO_ROUTE;
         } else {

@@ -8,7 +8,12 @@ rx_open_via_batch.
 And its TX-side lookups (neb_tx_table_*, neb_tx_resolve_batch[_host]): what consumeInsidePacket does
 per TUN read before it can send (inside.go:19-121) — newPacket, the broadcast, self and multicast
 gates, Hosts[vpnAddr], the unsafe routes' longest-prefix match and ECMP — for a whole TX batch in
-one call, in front of neb_tx_seal_batch / neb_tx_seal_via_batch (TxTable)."""
+one call, in front of neb_tx_seal_batch / neb_tx_seal_via_batch (TxTable).
+
+And the state of the RX inner resolve (neb_peer_table_*; the call itself is in outside.py): every
+tunnel's certificate networks as HostInfo.buildNetworks files them (hostmap.go:837-857) and the
+node's routable networks (firewall.go:154-165), for the two address checks of firewall.Drop on a
+whole opened batch (PeerTable, build_networks, routable)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -278,4 +283,109 @@ class TxTable:
     _stream = IndexTable._stream
 
 
-__all__ = ["IndexTable", "entries", "sources", "TxTable", "tx_addrs", "tx_hosts", "tx_routes", "tx_own"]
+def build_networks(my_networks: Sequence[str], cert_networks: Sequence[str],
+                   unsafe_networks: Sequence[str] = ()) -> list:
+    """HostInfo.buildNetworks (hostmap.go:837-857) -> [(prefix, type)] in insertion order, for
+    peer_nets() / PeerTable.update: every address of the peer's certificate at full length, VPN when
+    one of `my_networks` ("10.1.0.7/16": myVpnNetworksTable) contains it, else VPN_PEER; then the
+    certificate's unsafe networks. The simple case, for which the reference keeps no table and
+    compares with vpnAddrs[0], comes out as its equivalent: one full-length VPN entry."""
+    mine = [ipaddress.ip_interface(s).network for s in my_networks]
+    out = []
+    for s in cert_networks:
+        ip = ipaddress.ip_interface(s).ip
+        inside = any(n.version == ip.version and ip in n for n in mine)
+        out.append((f"{ip}/{ip.max_prefixlen}", L.NET_VPN if inside else L.NET_VPN_PEER))
+    return out + [(str(ipaddress.ip_network(s, strict=False)), L.NET_UNSAFE) for s in unsafe_networks]
+
+
+def routable(cert_networks: Sequence[str], unsafe_networks: Sequence[str] = ()) -> list:
+    """NewFirewall's routableNetworks (firewall.go:154-165) -> prefixes for PeerTable.set_routable: the
+    own certificate's addresses at full length, then its unsafe networks."""
+    own = [ipaddress.ip_interface(s).ip for s in cert_networks]
+    return [f"{ip}/{ip.max_prefixlen}" for ip in own] + [str(ipaddress.ip_network(s, strict=False)) for s in unsafe_networks]
+
+
+def _cidr_into(rec, prefix: str) -> None:
+    n = ipaddress.ip_interface(prefix)  # host bits are kept: the table masks them, as bart's Insert does
+    _addr_into(rec, str(n.ip))
+    rec["bits"] = n.network.prefixlen
+
+
+def peer_nets(rows: Iterable[Tuple[int, str, int]]) -> np.ndarray:
+    """[(tunnel, prefix, type)] -> PEER_NET_DTYPE"""
+    rows = list(rows)
+    out = np.zeros(len(rows), L.PEER_NET_DTYPE)
+    for k, (tunnel, prefix, typ) in enumerate(rows):
+        _cidr_into(out[k], prefix)
+        out[k]["tunnel"], out[k]["type"] = tunnel, typ
+    return out
+
+
+def peer_keys(rows: Iterable[Tuple[int, str]]) -> np.ndarray:
+    """[(tunnel, prefix)] -> PEER_KEY_DTYPE"""
+    rows = list(rows)
+    out = np.zeros(len(rows), L.PEER_KEY_DTYPE)
+    for k, (tunnel, prefix) in enumerate(rows):
+        _cidr_into(out[k], prefix)
+        out[k]["tunnel"] = tunnel
+    return out
+
+
+class PeerTable:
+    """One neb_peer_table: every tunnel's certificate networks (HostInfo.networks) and the node's
+    routable set, for the two address checks of firewall.Drop on opened packets. engine=None:
+    host-only (inner_host only)."""
+
+    def __init__(self, engine, capacity: int):
+        self.engine = engine
+        self.handle = C.c_void_p()
+        L.check(L.lib().neb_peer_table_create(engine.handle if engine is not None else None, capacity,
+                                              C.byref(self.handle)), "neb_peer_table_create")
+
+    def close(self) -> None:
+        if self.handle:
+            L.lib().neb_peer_table_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def update(self, delete=(), put=(), stream=None) -> None:
+        """delete: PEER_KEY_DTYPE or rows for peer_keys(), applied first; put: PEER_NET_DTYPE or rows
+        for peer_nets(). With an engine the device image follows on `stream` (torch's current one by
+        default)."""
+        dl = delete if isinstance(delete, np.ndarray) else peer_keys(delete)
+        pt = put if isinstance(put, np.ndarray) else peer_nets(put)
+        dl = np.ascontiguousarray(dl, dtype=L.PEER_KEY_DTYPE)
+        pt = np.ascontiguousarray(pt, dtype=L.PEER_NET_DTYPE)
+        L.check(L.lib().neb_peer_table_update(self.handle, _vp(dl), len(dl), _vp(pt), len(pt),
+                                              C.c_void_p(self._stream(stream))), "neb_peer_table_update")
+
+    def set_routable(self, prefixes: Sequence[str]) -> None:
+        """prefixes: routable()'s list."""
+        nets = np.zeros(len(prefixes), L.CIDR_DTYPE)
+        for k, s in enumerate(prefixes):
+            _cidr_into(nets[k], s)
+        L.check(L.lib().neb_peer_table_set_routable(self.handle, _vp(nets), len(nets)), "neb_peer_table_set_routable")
+
+    def count(self) -> int:
+        live = C.c_uint32()
+        L.check(L.lib().neb_peer_table_count(self.handle, C.byref(live)), "neb_peer_table_count")
+        return live.value
+
+    def probe(self, tunnel: int, prefix: str) -> Tuple[bool, int, int]:
+        """(found, slot, probes) from the host copy."""
+        key = peer_keys([(tunnel, prefix)])
+        out = (C.c_uint32 * 3)()
+        L.check(L.lib().neb_peer_table_probe(self.handle, _vp(key), out), "neb_peer_table_probe")
+        return bool(out[0]), out[1], out[2]
+
+    _stream = IndexTable._stream
+
+
+__all__ = ["IndexTable", "entries", "sources", "TxTable", "tx_addrs", "tx_hosts", "tx_routes", "tx_own", "PeerTable",
+           "build_networks", "routable", "peer_nets", "peer_keys"]

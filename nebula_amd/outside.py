@@ -82,6 +82,39 @@ def plain_from_wire_device(engine, d_packets, d_status, d_epoch, d_arena, d_plai
     L.check(rc, "neb_rx_plain_from_wire")
 
 
+def inner_host(table, packets: np.ndarray, status: np.ndarray, epoch: np.ndarray, arena: np.ndarray,
+               arena_len: Optional[int] = None, want_fw: bool = True):
+    """neb_rx_inner_batch_host over a hostmap.PeerTable: newPacket(incoming) and firewall.Drop's two
+    address checks on a finished rx_open_wire_batch. Returns (plain, fw or None, inner status)."""
+    pk = np.ascontiguousarray(packets, dtype=L.RX_PACKET_DTYPE)
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    ep = np.ascontiguousarray(epoch, dtype=np.uint64)
+    n = len(pk)
+    plain = np.zeros(max(n, 1), L.PLAIN_PACKET_DTYPE)
+    fw = np.zeros(max(n, 1), L.FW_PACKET_DTYPE) if want_fw else None
+    inner = np.zeros(max(n, 1), np.int32)
+    rc = L.lib().neb_rx_inner_batch_host(table.handle, _vp(pk), _vp(st), _vp(ep), len(ep), n, _vp(arena),
+                                         arena.nbytes if arena_len is None else arena_len, _vp(plain),
+                                         None if fw is None else _vp(fw), _vp(inner))
+    L.check(rc, "neb_rx_inner_batch_host")
+    return plain[:n], None if fw is None else fw[:n], inner[:n]
+
+
+def inner_device(engine, table, d_packets, d_status, d_epoch, d_arena, d_plain, d_fw=None, d_inner_status=None,
+                 stream=None) -> None:
+    """neb_rx_inner_batch over torch tensors (d_epoch: int64 holding the uint64 epochs; d_fw uint8 of
+    FW_PACKET_DTYPE records, d_inner_status int32, both optional). Only enqueues."""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    n = d_packets.numel() // L.RX_PACKET_DTYPE.itemsize
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = L.lib().neb_rx_inner_batch(engine.handle if engine is not None else None, table.handle, p(d_packets),
+                                    p(d_status), p(d_epoch), d_epoch.numel(), n, p(d_arena), p(d_plain), p(d_fw),
+                                    p(d_inner_status), C.c_void_p(s))
+    L.check(rc, "neb_rx_inner_batch")
+
+
 class TunWrite:
     """One write to the TUN: the virtio_net_hdr fields and the bytes."""
 
@@ -147,17 +180,23 @@ class MultiCoalescer:
 
 def receive(engine, alg: int, windows: DeviceWindows, d_packets, d_arena, d_status, d_epoch, d_plain, d_out,
             d_writes, d_nwrites, d_pkt_write, d_pkt_status, lanes: int = L.COALESCE_TCP | L.COALESCE_UDP,
-            key_hint: int = L.KEYS_MIXED, stream=None) -> None:
+            key_hint: int = L.KEYS_MIXED, stream=None, peers=None, d_fw=None, d_inner_status=None) -> None:
     """Wire packets to TUN writes on the device: neb_rx_open_wire_batch (the gate, the replay windows,
     Decrypt / VerifyRelay) -> neb_rx_plain_from_wire (opened data messages become commit records,
     epoch = d_epoch[key_id]) -> neb_rx_coalesce_batch. The caller marks firewall drops by or-ing
     PLAIN_SKIP into d_plain's flags between the last two steps if it filters; this composition commits
-    every opened data message. The outputs are valid once the stream is synchronized."""
+    every opened data message. With `peers` (a hostmap.PeerTable on the engine) neb_rx_inner_batch
+    takes the middle step's place: a packet whose inner source is not the peer's, or whose inner
+    destination is not ours, is not committed, and d_fw / d_inner_status (optional) say why. The
+    outputs are valid once the stream is synchronized."""
     rx_open_wire_batch_device(engine, alg, windows, d_packets, d_arena, d_status, key_hint, stream)
-    plain_from_wire_device(engine, d_packets, d_status, d_epoch, d_arena, d_plain, stream)
+    if peers is None:
+        plain_from_wire_device(engine, d_packets, d_status, d_epoch, d_arena, d_plain, stream)
+    else:
+        inner_device(engine, peers, d_packets, d_status, d_epoch, d_arena, d_plain, d_fw, d_inner_status, stream)
     coalesce_batch_device(engine, d_plain, d_arena, d_out, d_writes, d_nwrites, d_pkt_write, d_pkt_status, lanes,
                           stream)
 
 
 __all__ = ["MultiCoalescer", "TunWrite", "coalesce_batch_host", "coalesce_batch_device", "plain_from_wire_host",
-           "plain_from_wire_device", "receive"]
+           "plain_from_wire_device", "inner_host", "inner_device", "receive"]
