@@ -35,6 +35,9 @@
  *                            (overlay/batch/tx_batch.go:15-59)
  *   neb_tx_seal_via_batch    the same with its relay branch (inside.go:178-223): the segment
  *                            sealed under the target's key, then prepareSendVia (:442-501)
+ *   neb_tx_send_plan         batchWriter.WriteBatch's packing of a SendBatch into sendmmsg entries
+ *                            (udp/udp_linux_writebatch.go:194-252) with planRun's UDP_SEGMENT runs
+ *                            (:312-346), over the wires of a TX batch
  *   neb_rx_open_batch_host   ConnectionState.Decrypt (connection_state.go:99-119) over a whole
  *                            receive batch (the recvmmsg flush, interface.go:381-413): window
  *                            Check → DecryptDanger → window Update, results identical to the
@@ -599,6 +602,85 @@ NEB_API int neb_tx_seal_via_batch_host(neb_engine* e, int alg, neb_tx_tunnel* tu
                                        const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap,
                                        neb_tx_wire* wires, int32_t* wire_status, uint32_t max_wires,
                                        uint32_t* nwires, int32_t* packet_status, uint32_t key_hint);
+/* ---- TX send plan: sealed wires -> sendmmsg entries with UDP_SEGMENT runs ------------------------ */
+/* What batchWriter.WriteBatch does with a SendBatch before it calls sendmmsg
+ * (udp/udp_linux_writebatch.go:194-252, planRun :312-346), for the wires of a TX batch: consecutive
+ * packets to one destination become UDP_SEGMENT runs (equal sizes, a shorter packet only as the
+ * last; at most max_segments packets and NEB_SEND_MAX_BYTES bytes), destinations the socket cannot
+ * address are skipped, and the iovecs are packed into chunks of chunk_packets. The plan only names
+ * bytes: the caller builds mmsghdr, iovec and cmsg from it and sends. */
+#define NEB_STATUS_UNROUTABLE 16 /* send_status: the socket cannot address the destination: skipped */
+#define NEB_STATUS_NOT_SENT 17   /* send_status: wire_status != OK (never committed to the SendBatch) */
+#define NEB_SEND_NONE 0xFFFFFFFFu
+#define NEB_SEND_MAX_BYTES 65000 /* maxGSOBytes */
+typedef struct neb_udp_addr {    /* netip.AddrPort of hostinfo.remote; compared as these 20 bytes */
+    uint8_t addr[16];            /* family 4: addr[0..4), the rest 0 */
+    uint16_t port;
+    uint8_t family;              /* 0: no valid remote; 4; 6 */
+    uint8_t reserved;            /* 0 */
+} neb_udp_addr;
+typedef struct neb_send_iov { uint64_t off; uint32_t len; uint32_t wire; } neb_send_iov;   /* one iovec */
+typedef struct neb_send_entry {  /* one mmsghdr */
+    uint32_t iov_first;          /* iov[iov_first .. iov_first + niov) */
+    uint16_t niov;
+    uint16_t seg_size;           /* UDP_SEGMENT cmsg payload; 0 = no cmsg (niov == 1) */
+    uint32_t dst;                /* tunnel index whose remote[] is msg_name */
+    uint32_t bytes;              /* sum of the iov lengths */
+} neb_send_entry;
+/* Per wire i < *d_nwires, in wire order:
+ *   wire_status[i] != NEB_STATUS_OK: the packet was never committed (inside.go:137-145):
+ *   send_status[i] = NEB_STATUS_NOT_SENT, it is absent from the plan, and a run continues across it;
+ *   its destination tunnel is t = packets[wires[i].packet].tunnel, or via[t].tunnel when
+ *   wires[i].reserved has NEB_TX_WIRE_VIA (relayHostInfo.GetRemote(), inside.go:216). A packet
+ *   index >= npackets, a tunnel index >= ntunnels or a via index >= ntunnels (checked in that order;
+ *   a via wire with via == NULL counts as the last): NEB_STATUS_BAD_KEY; the wire is then unroutable
+ *   with a destination of its own, so it breaks runs;
+ *   remote[t] not addressable by the socket: NEB_STATUS_UNROUTABLE, in no entry. Family 4 is always
+ *   addressable; family 6 on a v6 socket (socket_v4 == 0), and on a v4 socket when the address is in
+ *   ::ffff:0:0/96 (Unmap, udp_linux.go:371-376). Any other family is not. Deviation: family 0 (no
+ *   valid remote) is unroutable on either socket, where the reference never commits a packet to an
+ *   invalid direct remote at all (inside.go:178). Unroutable wires take no iovec, but they are
+ *   among WriteBatch's bufs and break runs, because their destination differs;
+ *   otherwise NEB_STATUS_OK: the wire is in exactly one entry, wire_entry[i]; every other wire has
+ *   wire_entry[i] = NEB_SEND_NONE.
+ * The wires that are not NOT_SENT are WriteBatch's bufs with addrs[] = remote[t] (compared as 20
+ * bytes), and planRun applies with maxGSOSegments = max_segments (<= 1: GSO is off, every packet is
+ * its own entry) and maxGSOBytes = NEB_SEND_MAX_BYTES: a packet of size 0 or above the byte cap is a
+ * run of one; a next packet that is empty, longer, to another destination or past a cap ends the
+ * run; a shorter one joins the run and ends it.
+ * Chunks: a chunk holds chunk_packets iovecs (the reference's scratch has 128; 0 = unlimited) and no
+ * run crosses a chunk. Skipped runs use no iovec, so chunk c is exactly
+ * iov[c * chunk_packets .. (c + 1) * chunk_packets): the entries of one sendmmsg call are those whose
+ * iov_first lies in that span, and the caller derives each call's span from iov_first alone.
+ * Entries are in wire order. seg_size is the first packet's length when niov >= 2, else 0; dst is
+ * the first wire's destination tunnel; iov[k] is {wires[w].out_off, wires[w].len, w}. *niov and
+ * *nentries get the counts. iov, entries, wire_entry and send_status hold max_wires elements each,
+ * which nothing can overflow; elements past the counts (past *d_nwires for the per-wire arrays) are
+ * not written.
+ * Device pointers (d_iov 8-byte, d_remote and the others 4-byte aligned); asynchronous on `stream`:
+ * *d_nwires (clamped to max_wires) is read on the device, with no read-back and no synchronisation,
+ * so the call can follow neb_tx_seal_batch / neb_tx_seal_via_batch on their stream directly. Its cost
+ * follows max_wires, not *d_nwires. max_wires == 0 returns NEB_OK and writes nothing.
+ * NEB_ERR_INVALID: max_segments > 1024, or a required array is NULL (every one but d_via; d_packets
+ * and d_remote may be NULL when their count is 0).
+ * Not part of the plan: resuming a partial send, and the EIO path that disables GSO and replays:
+ * after an EIO on an entry with niov >= 2 the caller plans again with max_segments = 1. */
+NEB_API int neb_tx_send_plan(neb_engine* e, const neb_tx_wire* d_wires, const int32_t* d_wire_status,
+                             const uint32_t* d_nwires, uint32_t max_wires, const neb_tx_packet* d_packets,
+                             uint32_t npackets, const neb_relay_route* d_via /* may be NULL */,
+                             const neb_udp_addr* d_remote, uint32_t ntunnels, uint32_t socket_v4,
+                             uint32_t max_segments, uint32_t chunk_packets, neb_send_iov* d_iov, uint32_t* d_niov,
+                             neb_send_entry* d_entries, uint32_t* d_nentries, uint32_t* d_wire_entry,
+                             int32_t* d_send_status, void* stream);
+/* The same over host memory with nwires by value: the plain sequential loop, no engine, no GPU. The
+ * four output arrays hold nwires elements. */
+NEB_API int neb_tx_send_plan_host(const neb_tx_wire* wires, const int32_t* wire_status, uint32_t nwires,
+                                  const neb_tx_packet* packets, uint32_t npackets,
+                                  const neb_relay_route* via /* may be NULL */, const neb_udp_addr* remote,
+                                  uint32_t ntunnels, uint32_t socket_v4, uint32_t max_segments,
+                                  uint32_t chunk_packets, neb_send_iov* iov, uint32_t* niov,
+                                  neb_send_entry* entries, uint32_t* nentries, uint32_t* wire_entry,
+                                  int32_t* send_status);
 /* ---- receive: opened packets -> TUN writes (TSO / USO superpackets) ---------------------------- */
 /* What the reference does between the open and the TUN write: MultiCoalescer.Commit per packet, then
  * Flush (overlay/batch/multi_coalesce.go): sort by (epoch, counter), coalesce in-flow TCP / UDP runs

@@ -44,6 +44,8 @@ STATUS_NO_TUNNEL = 12  # neb_tx_resolve_batch: no host entry yet, the caller han
 STATUS_RX_BAD_REMOTE = 13  # neb_rx_inner_batch: ErrInvalidRemoteIP
 STATUS_RX_PEER_REJECTED = 14  # neb_rx_inner_batch: ErrPeerRejected
 STATUS_RX_BAD_LOCAL = 15  # neb_rx_inner_batch: ErrInvalidLocalIP
+STATUS_UNROUTABLE = 16  # neb_tx_send_plan: the socket cannot address the destination
+STATUS_NOT_SENT = 17  # neb_tx_send_plan: wire_status != OK, never committed to the SendBatch
 
 OVERHEAD = 16
 HEADER_LEN = 16
@@ -127,6 +129,15 @@ COALESCE_TCP, COALESCE_UDP = 1, 2
 WRITE_NONE = 0xFFFFFFFF
 VNET_F_NEEDS_CSUM, VNET_F_DATA_VALID = 1, 2
 
+# neb_tx_send_plan (include/nebula_aead.h): sealed wires -> sendmmsg entries
+SEND_NONE = 0xFFFFFFFF
+SEND_MAX_BYTES = 65000
+UDP_ADDR_DTYPE = np.dtype([("addr", "u1", (16,)), ("port", "<u2"), ("family", "u1"), ("reserved", "u1")])
+SEND_IOV_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("wire", "<u4")])
+SEND_ENTRY_DTYPE = np.dtype([("iov_first", "<u4"), ("niov", "<u2"), ("seg_size", "<u2"), ("dst", "<u4"),
+                             ("bytes", "<u4")])
+assert UDP_ADDR_DTYPE.itemsize == 20 and SEND_IOV_DTYPE.itemsize == 16 and SEND_ENTRY_DTYPE.itemsize == 16
+
 # Every symbol include/nebula_aead.h declares, with (restype, argtypes).
 _vp, _u8p, _sz, _u32, _u64, _i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
 SIGNATURES = {
@@ -189,6 +200,10 @@ SIGNATURES = {
     "neb_rx_open_via_batch": (_i, [_vp, _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "neb_rx_open_via_batch_host": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _vp, _vp, _vp, _u32, _u32]),
     "neb_rx_via_unwrap_host": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
+    "neb_tx_send_plan": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp]),
+    "neb_tx_send_plan_host": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
     "neb_rx_coalesce_batch": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "neb_rx_coalesce_batch_host": (_i, [_vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _vp, _u32]),
     "neb_rx_plain_from_wire": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),

@@ -39,6 +39,7 @@
 #include "timing.hpp"
 #include "tx.hpp"
 #include "coalesce.hpp"
+#include "send.hpp"
 #include "cipher.hpp"
 #include "engine_internal.hpp"
 
@@ -114,6 +115,14 @@ struct CoSpace {
     neb::HipWorkspace<> dev;
     uint32_t n_cap = 0;
     neb::CoWs ws{};
+    std::mutex mu;
+};
+
+// Device workspace of the TX send plan (send.hpp).
+struct SendSpace {
+    neb::HipWorkspace<> dev;
+    uint32_t n_cap = 0;
+    neb::SendWs ws{};
     std::mutex mu;
 };
 
@@ -229,6 +238,7 @@ struct neb_engine {
     SchedSpace sched;
     TxSpace tx;
     CoSpace co;
+    SendSpace send;
 
     // The host receive's zero-copy open (neb::RxStaging, window.cpp): a stream and mixed-key
     // workspace of its own, descriptors and statuses staged in pinned memory, one event.
@@ -1660,6 +1670,48 @@ NEB_API int neb_rx_plain_from_wire(neb_engine* e, const neb_rx_packet* d_pk, con
     if (n == 0) return NEB_OK;
     DeviceGuard dg(e->device);
     HIP_TRY(neb_co_plain_from_wire(d_pk, d_status, d_epoch, nepoch, n, d_arena, d_plain, (hipStream_t)stream));
+    return NEB_OK;
+}
+
+// ---- TX send plan (send.hip) ---------------------------------------------------------------------
+
+static hipError_t send_reserve(neb_engine* e, uint32_t n) {
+    SendSpace& sp = e->send;
+    if (sp.dev.mem() && n <= sp.n_cap) return hipSuccess;
+    const uint32_t nc = std::max({n, sp.n_cap, 1024u});
+    size_t cub = 0;
+    const size_t bytes = neb_send_ws_bytes(nc, &cub);
+    sp.n_cap = 0;
+    hipError_t err = sp.dev.reserve(bytes);  // (laid out again whether it grew or not: the capacity changed)
+    if (err != hipSuccess) return err;
+    neb::send_ws_layout(nc, cub, sp.dev.mem(), &sp.ws);
+    sp.n_cap = nc;
+    return hipSuccess;
+}
+
+NEB_API int neb_tx_send_plan(neb_engine* e, const neb_tx_wire* d_wires, const int32_t* d_wire_status,
+                             const uint32_t* d_nwires, uint32_t max_wires, const neb_tx_packet* d_packets,
+                             uint32_t npackets, const neb_relay_route* d_via, const neb_udp_addr* d_remote,
+                             uint32_t ntunnels, uint32_t socket_v4, uint32_t max_segments, uint32_t chunk_packets,
+                             neb_send_iov* d_iov, uint32_t* d_niov, neb_send_entry* d_entries, uint32_t* d_nentries,
+                             uint32_t* d_wire_entry, int32_t* d_send_status, void* stream) {
+    if (!e || max_segments > neb::kSendMaxSegments || max_wires > 0x7FFFFFFFu || !d_nwires || !d_niov || !d_nentries ||
+        (npackets && !d_packets) || (ntunnels && !d_remote) || (reinterpret_cast<uintptr_t>(d_remote) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_iov) & 7u) ||
+        (max_wires && (!d_wires || !d_wire_status || !d_iov || !d_entries || !d_wire_entry || !d_send_status)))
+        return NEB_ERR_INVALID;
+    if (max_wires == 0) return NEB_OK;
+    DeviceGuard dg(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(e->send.mu);
+    SendSpace& sp = e->send;
+    HIP_TRY(send_reserve(e, max_wires));
+    HIP_TRY(sp.dev.begin(s));
+    neb::SendArgs a{d_wires, d_wire_status, d_nwires, d_packets, d_via, d_remote, d_iov, d_niov, d_entries, d_nentries,
+                    d_wire_entry, d_send_status, max_wires, npackets, ntunnels, socket_v4, max_segments, chunk_packets,
+                    sp.ws};
+    HIP_TRY(neb_send_run(&a, s));
+    HIP_TRY(sp.dev.end(s));
     return NEB_OK;
 }
 

@@ -173,5 +173,83 @@ class DeviceTxBatch:
                         self.pk_status.cpu().numpy(), self.tunnels.cpu().numpy().view(TX_TUNNEL_DTYPE).copy())
 
 
+@dataclass
+class SendPlan:
+    """neb_tx_send_plan's six outputs (udp/udp_linux_writebatch.go:194-252: what WriteBatch packs)."""
+    iov: np.ndarray          # SEND_IOV_DTYPE, niov of them
+    entries: np.ndarray      # SEND_ENTRY_DTYPE, nentries of them
+    wire_entry: np.ndarray   # per wire: its entry or SEND_NONE
+    send_status: np.ndarray  # per wire: OK / NOT_SENT / UNROUTABLE / BAD_KEY
+
+
+def send_plan_host(wires: np.ndarray, wire_status: np.ndarray, packets: np.ndarray, via, remote: np.ndarray,
+                   socket_v4: bool, max_segments: int, chunk_packets: int = 128) -> SendPlan:
+    """WriteBatch's packing of the sealed wires of a TX batch, held in host memory: no engine, no GPU."""
+    lib = L.lib()
+    wires = np.ascontiguousarray(wires, dtype=TX_WIRE_DTYPE)
+    wst = np.ascontiguousarray(wire_status, dtype=np.int32)
+    packets = np.ascontiguousarray(packets, dtype=TX_PACKET_DTYPE)
+    remote = np.ascontiguousarray(remote, dtype=L.UDP_ADDR_DTYPE)
+    via = None if via is None else _via_array(via, len(remote))
+    n = len(wires)
+    if len(wst) != n:
+        raise ValueError("wire_status needs one entry per wire")
+    iov = np.zeros(n, L.SEND_IOV_DTYPE)
+    entries = np.zeros(n, L.SEND_ENTRY_DTYPE)
+    went = np.zeros(n, np.uint32)
+    sst = np.zeros(n, np.int32)
+    ni, ne = C.c_uint32(0), C.c_uint32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = lib.neb_tx_send_plan_host(vp(wires), vp(wst), n, vp(packets), len(packets), None if via is None else vp(via),
+                                   vp(remote), len(remote), int(bool(socket_v4)), max_segments, chunk_packets, vp(iov),
+                                   C.byref(ni), vp(entries), C.byref(ne), vp(went), vp(sst))
+    L.check(rc, "neb_tx_send_plan_host")
+    return SendPlan(iov[:ni.value].copy(), entries[:ne.value].copy(), went, sst)
+
+
+class DeviceSendPlan:
+    """The send plan of a DeviceTxBatch's wires, resident in device memory: `plan()` runs
+    neb_tx_send_plan on torch's current stream behind the batch's seal, with no synchronisation
+    between them; `result()` downloads the plan."""
+
+    def __init__(self, batch: "DeviceTxBatch", remote: np.ndarray, socket_v4: bool, max_segments: int,
+                 chunk_packets: int = 128):
+        import torch
+
+        dev = batch.wires.device
+        remote = np.ascontiguousarray(remote, dtype=L.UDP_ADDR_DTYPE)
+        if len(remote) != batch.ntun:
+            raise ValueError("remote needs one neb_udp_addr per tunnel")
+        self.batch = batch
+        self.remote = torch.from_numpy(remote.view(np.uint8).copy()).to(dev)
+        self.socket_v4, self.max_segments, self.chunk_packets = int(bool(socket_v4)), max_segments, chunk_packets
+        n = batch.max_wires
+        self.iov = torch.zeros(n * L.SEND_IOV_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.entries = torch.zeros(n * L.SEND_ENTRY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.wire_entry = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.send_status = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(2, dtype=torch.int32, device=dev)  # niov, nentries
+
+    def plan(self) -> None:
+        import torch
+
+        b = self.batch
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        rc = L.lib().neb_tx_send_plan(b.engine.handle, p(b.wires), p(b.wire_status), p(b.nwires), b.max_wires,
+                                      p(b.packets), b.npk, None if b.via is None else p(b.via), p(self.remote), b.ntun,
+                                      self.socket_v4, self.max_segments, self.chunk_packets, p(self.iov),
+                                      C.c_void_p(self.counts.data_ptr()), p(self.entries),
+                                      C.c_void_p(self.counts.data_ptr() + 4), p(self.wire_entry), p(self.send_status),
+                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        L.check(rc, "neb_tx_send_plan")
+
+    def result(self) -> SendPlan:
+        n = int(self.batch.nwires.cpu()[0])
+        ni, ne = (int(x) for x in self.counts.cpu())
+        return SendPlan(self.iov.cpu().numpy().view(L.SEND_IOV_DTYPE)[:ni].copy(),
+                        self.entries.cpu().numpy().view(L.SEND_ENTRY_DTYPE)[:ne].copy(),
+                        self.wire_entry.cpu().numpy().view(np.uint32)[:n].copy(), self.send_status.cpu().numpy()[:n].copy())
+
+
 __all__ = ["TX_PACKET_DTYPE", "TX_TUNNEL_DTYPE", "TX_WIRE_DTYPE", "tx_seal_batch_host", "tx_seal_via_batch_host",
-           "DeviceTxBatch", "TxResult", "slot_bytes", "slot_bytes_via"]
+           "DeviceTxBatch", "TxResult", "slot_bytes", "slot_bytes_via", "SendPlan", "send_plan_host", "DeviceSendPlan"]
