@@ -38,6 +38,8 @@
  *   neb_tx_send_plan         batchWriter.WriteBatch's packing of a SendBatch into sendmmsg entries
  *                            (udp/udp_linux_writebatch.go:194-252) with planRun's UDP_SEGMENT runs
  *                            (:312-346), over the wires of a TX batch
+ *   neb_rx_recv_plan         StdConn.ListenOut's split of a recvmmsg batch with UDP_GRO into wire
+ *                            packets: getFrom, parseRecvCmsg, deliverSegments (udp/udp_linux.go:237-331)
  *   neb_rx_open_batch_host   ConnectionState.Decrypt (connection_state.go:99-119) over a whole
  *                            receive batch (the recvmmsg flush, interface.go:381-413): window
  *                            Check → DecryptDanger → window Update, results identical to the
@@ -833,6 +835,76 @@ NEB_API int neb_rx_resolve_batch(neb_engine* e, const neb_index_table* t, neb_rx
 NEB_API int neb_rx_resolve_batch_host(const neb_index_table* t, neb_rx_packet* pk, const neb_rx_source* src,
                                       uint32_t n, const uint8_t* arena, size_t arena_len, neb_relay_route* route,
                                       neb_rx_via* via);
+/* ---- RX receive plan: UDP_GRO receive entries -> wire packets ----------------------------------- */
+/* What StdConn.ListenOut does with a recvmmsg batch before readOutsidePackets sees a packet
+ * (udp/udp_linux.go:274-284): with UDP_GRO on (udp_linux.go:78-108) one entry is a superdatagram, a
+ * gso_size in a control message and a raw sockaddr, and getFrom (:237-246), parseRecvCmsg (:307-331)
+ * and deliverSegments (:291-303) turn it into wire packets. The call does that for a whole batch and
+ * writes the neb_rx_packet / neb_rx_source arrays neb_rx_resolve_batch takes. The plan only names
+ * bytes: it never reads the arena. */
+#define NEB_RECV_NONE 0xFFFFFFFFu
+typedef struct neb_recv_entry {   /* one recvmmsg slot after the call; 48 bytes, 8-byte aligned */
+    uint64_t off;                 /* the slot's buffer in the arena */
+    uint32_t len;                 /* mmsghdr.msg_len */
+    int32_t  seg_size;            /* the UDP_GRO size when the caller parsed it (d_ctrl == NULL) */
+    uint8_t  name[28];            /* msg_name as the kernel wrote it (sockaddr_in / sockaddr_in6) */
+    uint32_t ctrl_len;            /* msg_controllen after the call (d_ctrl != NULL) */
+} neb_recv_entry;
+/* Per entry j, in entry order:
+ *   its segment size is entries[j].seg_size when d_ctrl == NULL; otherwise parseRecvCmsg over the L =
+ *   min(ctrl_len, ctrl_stride) bytes at d_ctrl + j * ctrl_stride, and no byte at or past L is read.
+ *   Linux LP64, little-endian: cmsghdr = {u64 len; i32 level; i32 type}, SizeofCmsghdr = CmsgLen(0) =
+ *   16, CmsgSpace(n) = 16 + align8(n). The walk starts at 0 with size 0 and is the reference's, hostile
+ *   input included: it stops when off + 16 > L; it returns what it has when len < 16 or len > L - off
+ *   (len as the reference's signed int, so 2^63 is negative); at level SOL_UDP (17), type UDP_GRO (104),
+ *   if off + 16 + 4 <= L the size is the int32 at off + 16, and the last match wins; it advances by
+ *   align8(len);
+ *   its packets are deliverSegments': size <= 0 or size >= len gives one packet {off, len} (len == 0
+ *   too: one empty packet); otherwise ceil(len / size) packets, packet k = {off + k * size, min(size,
+ *   len - k * size)}, offsets in 64 bits. Every entry yields at least one packet;
+ *   its source is getFrom's: the port is big-endian at name[2:4]; the address is name[4:8] when
+ *   socket_v4 != 0, else name[8:24], unmapped: an address in ::ffff:0:0/96 becomes family 4 with its
+ *   last four bytes. The sockaddr's family field and its other bytes are ignored, as there.
+ * Packets are numbered in entry order: first[j] is the sum of the counts before j, carried in 64 bits
+ * (one entry may hold 2^32 - 1 one-byte packets). Entry j is emitted iff first[j] + count[j] <=
+ * max_packets, so the emitted entries are a prefix: counts[1] = nentries_done is its length and
+ * counts[0] = npackets its packets. An emitted entry has entry_first[j] = first[j]; every other one
+ * has NEB_RECV_NONE and emits nothing: the caller plans it again with its next batch.
+ * Per emitted packet i of entry j: pk[i] = {off, len, NEB_KEYS_MIXED} (NEB_RX_OWN_SOURCE is never
+ * set: the resolve does that), pkt_entry[i] = j, src[i] = the source as neb_rx_resolve_batch wants it
+ * (for family 4 the address's other 12 bytes zero, reserved zero). Per entry j < nentries, emitted or
+ * not: from[j] = the source with its port (family 4 or 6, unused address bytes and reserved zero),
+ * for a later roaming check, which needs the port.
+ * Slots i in [npackets, max_packets) are written as padding: pk[i] = {0, 0, NEB_KEYS_MIXED},
+ * src[i] all zero (family 0), pkt_entry[i] = NEB_RECV_NONE. Unlike the send plan: neb_rx_resolve_batch
+ * and neb_rx_open_wire_batch take n by value, so a caller runs them over max_packets on the same
+ * stream with no read-back; their gate gives padding NEB_STATUS_INVALID and touches nothing. The
+ * call's cost follows nentries + max_packets. pk, src and pkt_entry hold max_packets elements, from
+ * and entry_first nentries, counts two; nothing beyond is written. src, pkt_entry and from may be
+ * NULL: not written.
+ * nentries == 0: counts = {0, 0}, every slot padding. max_packets == 0: counts = {0, 0}, every entry
+ * NEB_RECV_NONE.
+ * Device pointers (d_entries and d_ctrl 8-byte, the others 4-byte aligned); asynchronous on `stream`,
+ * no read-back, no synchronisation, so neb_rx_resolve_batch and the receive calls follow it on its
+ * stream directly.
+ * NEB_ERR_INVALID: e, d_pk, d_entry_first or d_counts NULL; d_entries NULL with nentries != 0;
+ * nentries or max_packets >= 2^31; d_ctrl given with a ctrl_stride of 0, not a multiple of 8, or
+ * above 1024; d_entries or d_ctrl not 8-byte aligned.
+ * Not part of the plan: the socket, recvmmsg, and handleHostRoaming (outside.go), whose allow-list
+ * and time-based suppression are control plane; from[] and pkt_entry[] are what it would read. */
+NEB_API int neb_rx_recv_plan(neb_engine* e, const neb_recv_entry* d_entries, uint32_t nentries,
+                             const uint8_t* d_ctrl /* may be NULL */, uint32_t ctrl_stride, uint32_t socket_v4,
+                             neb_rx_packet* d_pk, neb_rx_source* d_src /* may be NULL */,
+                             uint32_t* d_pkt_entry /* may be NULL */, uint32_t max_packets,
+                             neb_udp_addr* d_from /* may be NULL */, uint32_t* d_entry_first,
+                             uint32_t* d_counts /* {npackets, nentries_done} */, void* stream);
+/* The same over host memory: the plain sequential loop, no engine, no GPU. */
+NEB_API int neb_rx_recv_plan_host(const neb_recv_entry* entries, uint32_t nentries,
+                                  const uint8_t* ctrl /* may be NULL */, uint32_t ctrl_stride, uint32_t socket_v4,
+                                  neb_rx_packet* pk, neb_rx_source* src /* may be NULL */,
+                                  uint32_t* pkt_entry /* may be NULL */, uint32_t max_packets,
+                                  neb_udp_addr* from /* may be NULL */, uint32_t* entry_first,
+                                  uint32_t* counts /* {npackets, nentries_done} */);
 /* ---- TX resolve: parse, own-address gates and VPN address / route lookup for a TX batch -------- */
 /* The front half of consumeInsidePacket (inside.go:19-121) for a whole batch of TUN reads: newPacket
  * (outside.go:320-472, iputil/packet.go:349-395), the local-broadcast, self and multicast gates

@@ -138,6 +138,12 @@ SEND_ENTRY_DTYPE = np.dtype([("iov_first", "<u4"), ("niov", "<u2"), ("seg_size",
                              ("bytes", "<u4")])
 assert UDP_ADDR_DTYPE.itemsize == 20 and SEND_IOV_DTYPE.itemsize == 16 and SEND_ENTRY_DTYPE.itemsize == 16
 
+# neb_rx_recv_plan (include/nebula_aead.h): recvmmsg entries with UDP_GRO -> wire packets
+RECV_NONE = 0xFFFFFFFF
+RECV_ENTRY_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("seg_size", "<i4"), ("name", "u1", (28,)),
+                             ("ctrl_len", "<u4")])
+assert RECV_ENTRY_DTYPE.itemsize == 48
+
 # Every symbol include/nebula_aead.h declares, with (restype, argtypes).
 _vp, _u8p, _sz, _u32, _u64, _i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
 SIGNATURES = {
@@ -216,6 +222,8 @@ SIGNATURES = {
     "neb_index_table_probe": (_i, [_vp, _u32, _u32, C.POINTER(_u32)]),
     "neb_rx_resolve_batch": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "neb_rx_resolve_batch_host": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
+    "neb_rx_recv_plan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "neb_rx_recv_plan_host": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "neb_tx_table_create": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "neb_tx_table_destroy": (_i, [_vp]),
     "neb_tx_table_update_hosts": (_i, [_vp, _vp, _u32, _vp, _u32, _vp]),

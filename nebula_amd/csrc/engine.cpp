@@ -39,6 +39,7 @@
 #include "timing.hpp"
 #include "tx.hpp"
 #include "coalesce.hpp"
+#include "recv.hpp"
 #include "send.hpp"
 #include "cipher.hpp"
 #include "engine_internal.hpp"
@@ -123,6 +124,14 @@ struct SendSpace {
     neb::HipWorkspace<> dev;
     uint32_t n_cap = 0;
     neb::SendWs ws{};
+    std::mutex mu;
+};
+
+// Device workspace of the RX receive plan (recv.hpp).
+struct RecvSpace {
+    neb::HipWorkspace<> dev;
+    uint32_t n_cap = 0;
+    neb::RecvWs ws{};
     std::mutex mu;
 };
 
@@ -239,6 +248,7 @@ struct neb_engine {
     TxSpace tx;
     CoSpace co;
     SendSpace send;
+    RecvSpace recv;
 
     // The host receive's zero-copy open (neb::RxStaging, window.cpp): a stream and mixed-key
     // workspace of its own, descriptors and statuses staged in pinned memory, one event.
@@ -1711,6 +1721,44 @@ NEB_API int neb_tx_send_plan(neb_engine* e, const neb_tx_wire* d_wires, const in
                     d_wire_entry, d_send_status, max_wires, npackets, ntunnels, socket_v4, max_segments, chunk_packets,
                     sp.ws};
     HIP_TRY(neb_send_run(&a, s));
+    HIP_TRY(sp.dev.end(s));
+    return NEB_OK;
+}
+
+// ---- RX receive plan (recv.hip) ------------------------------------------------------------------
+
+static hipError_t recv_reserve(neb_engine* e, uint32_t n) {
+    RecvSpace& sp = e->recv;
+    if (sp.dev.mem() && n <= sp.n_cap) return hipSuccess;
+    const uint32_t nc = std::max({n, sp.n_cap, 1024u});
+    size_t cub = 0;
+    const size_t bytes = neb_recv_ws_bytes(nc, &cub);
+    sp.n_cap = 0;
+    hipError_t err = sp.dev.reserve(bytes);  // (laid out again whether it grew or not: the capacity changed)
+    if (err != hipSuccess) return err;
+    neb::recv_ws_layout(nc, cub, sp.dev.mem(), &sp.ws);
+    sp.n_cap = nc;
+    return hipSuccess;
+}
+
+NEB_API int neb_rx_recv_plan(neb_engine* e, const neb_recv_entry* d_entries, uint32_t nentries, const uint8_t* d_ctrl,
+                             uint32_t ctrl_stride, uint32_t socket_v4, neb_rx_packet* d_pk, neb_rx_source* d_src,
+                             uint32_t* d_pkt_entry, uint32_t max_packets, neb_udp_addr* d_from, uint32_t* d_entry_first,
+                             uint32_t* d_counts, void* stream) {
+    if (!e || !d_pk || !d_entry_first || !d_counts || (nentries && !d_entries) || nentries > 0x7FFFFFFFu ||
+        max_packets > 0x7FFFFFFFu ||
+        (d_ctrl && (ctrl_stride == 0u || (ctrl_stride & 7u) || ctrl_stride > neb::kRecvMaxCtrlStride)) ||
+        (reinterpret_cast<uintptr_t>(d_entries) & 7u) || (reinterpret_cast<uintptr_t>(d_ctrl) & 7u))
+        return NEB_ERR_INVALID;
+    DeviceGuard dg(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(e->recv.mu);
+    RecvSpace& sp = e->recv;
+    HIP_TRY(recv_reserve(e, nentries));
+    HIP_TRY(sp.dev.begin(s));
+    neb::RecvArgs a{d_entries, d_ctrl, d_pk, d_src, d_pkt_entry, d_from, d_entry_first, d_counts,
+                    nentries, max_packets, ctrl_stride, socket_v4, sp.ws};
+    HIP_TRY(neb_recv_run(&a, s));
     HIP_TRY(sp.dev.end(s));
     return NEB_OK;
 }

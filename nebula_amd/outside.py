@@ -5,7 +5,10 @@ pass the rest through, and give every TUN write its virtio_net_hdr fields.
 
 The host form runs on the CPU (one routine's 64-packet flush); the device form keeps a batch that
 neb_rx_open_wire_batch opened on the device there: receive() composes the two with
-neb_rx_plain_from_wire in between."""
+neb_rx_plain_from_wire in between.
+
+And the receive side before the resolve (neb_rx_recv_plan[_host]): ListenOut's split of a recvmmsg
+batch with UDP_GRO into wire packets (udp/udp_linux.go:237-331), recv_plan_host / recv_plan_device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -115,6 +118,56 @@ def inner_device(engine, table, d_packets, d_status, d_epoch, d_arena, d_plain, 
     L.check(rc, "neb_rx_inner_batch")
 
 
+def recv_plan_host(entries: np.ndarray, socket_v4: bool, max_packets: int, ctrl: Optional[np.ndarray] = None,
+                   ctrl_stride: int = 0):
+    """neb_rx_recv_plan_host: what ListenOut does with a recvmmsg batch under UDP_GRO
+    (udp/udp_linux.go:237-331). entries: RECV_ENTRY_DTYPE; ctrl: the control slots, ctrl_stride bytes
+    each (None: the entries' seg_size is used). Returns (packets, sources, pkt_entry, all three over
+    max_packets slots with the padding; from per entry; entry_first; npackets; nentries_done)."""
+    en = np.ascontiguousarray(entries, dtype=L.RECV_ENTRY_DTYPE)
+    n = len(en)
+    pk = np.zeros(max(max_packets, 1), L.RX_PACKET_DTYPE)
+    src = np.zeros(max(max_packets, 1), L.RX_SOURCE_DTYPE)
+    pe = np.zeros(max(max_packets, 1), np.uint32)
+    frm = np.zeros(max(n, 1), L.UDP_ADDR_DTYPE)
+    first = np.zeros(max(n, 1), np.uint32)
+    counts = np.zeros(2, np.uint32)
+    if ctrl is not None:
+        ctrl = np.ascontiguousarray(ctrl, dtype=np.uint8)
+        if ctrl.nbytes < n * ctrl_stride:
+            raise ValueError("one control slot per entry")
+    rc = L.lib().neb_rx_recv_plan_host(_vp(en), n, None if ctrl is None else _vp(ctrl), ctrl_stride, int(socket_v4),
+                                       _vp(pk), _vp(src), _vp(pe), max_packets, _vp(frm), _vp(first), _vp(counts))
+    L.check(rc, "neb_rx_recv_plan_host")
+    return pk[:max_packets], src[:max_packets], pe[:max_packets], frm[:n], first[:n], int(counts[0]), int(counts[1])
+
+
+def recv_plan_device(engine, d_entries, socket_v4: bool, d_packets, d_entry_first, d_counts, d_src=None,
+                     d_pkt_entry=None, d_from=None, d_ctrl=None, ctrl_stride: int = 0, stream=None) -> None:
+    """neb_rx_recv_plan over torch tensors on the engine's device: d_entries uint8 of RECV_ENTRY_DTYPE
+    records, d_ctrl uint8 control slots of ctrl_stride bytes (None: the entries' seg_size), d_packets
+    uint8 of RX_PACKET_DTYPE records (max_packets = its capacity), d_src uint8 of RX_SOURCE_DTYPE,
+    d_pkt_entry int32 per packet, d_from uint8 of UDP_ADDR_DTYPE and d_entry_first int32 per entry,
+    d_counts two int32 {npackets, nentries_done}. Only enqueues: neb_rx_resolve_batch and the receive
+    calls follow over all of d_packets on the same stream (torch's current one by default)."""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    n = d_entries.numel() // L.RECV_ENTRY_DTYPE.itemsize
+    mp = d_packets.numel() // L.RX_PACKET_DTYPE.itemsize
+    if d_ctrl is not None and d_ctrl.numel() < n * ctrl_stride:
+        raise ValueError("one control slot per entry")
+    for t, per, cnt in ((d_src, L.RX_SOURCE_DTYPE.itemsize, mp), (d_pkt_entry, 1, mp), (d_from, L.UDP_ADDR_DTYPE.itemsize, n),
+                        (d_entry_first, 1, n)):
+        if t is not None and t.numel() // per < cnt:
+            raise ValueError("an output is shorter than its count")
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = L.lib().neb_rx_recv_plan(engine.handle, p(d_entries) if n else None, n, p(d_ctrl), ctrl_stride, int(socket_v4),
+                                  p(d_packets), p(d_src), p(d_pkt_entry), mp, p(d_from), p(d_entry_first), p(d_counts),
+                                  C.c_void_p(s))
+    L.check(rc, "neb_rx_recv_plan")
+
+
 class TunWrite:
     """One write to the TUN: the virtio_net_hdr fields and the bytes."""
 
@@ -199,4 +252,4 @@ def receive(engine, alg: int, windows: DeviceWindows, d_packets, d_arena, d_stat
 
 
 __all__ = ["MultiCoalescer", "TunWrite", "coalesce_batch_host", "coalesce_batch_device", "plain_from_wire_host",
-           "plain_from_wire_device", "inner_host", "inner_device", "receive"]
+           "plain_from_wire_device", "inner_host", "inner_device", "receive", "recv_plan_host", "recv_plan_device"]
