@@ -891,7 +891,8 @@ typedef struct neb_recv_entry {   /* one recvmmsg slot after the call; 48 bytes,
  * nentries or max_packets >= 2^31; d_ctrl given with a ctrl_stride of 0, not a multiple of 8, or
  * above 1024; d_entries or d_ctrl not 8-byte aligned.
  * Not part of the plan: the socket, recvmmsg, and handleHostRoaming (outside.go), whose allow-list
- * and time-based suppression are control plane; from[] and pkt_entry[] are what it would read. */
+ * and time-based suppression are control plane; from[] and pkt_entry[] are what it reads, reduced to
+ * one record per run by neb_rx_report_batch. */
 NEB_API int neb_rx_recv_plan(neb_engine* e, const neb_recv_entry* d_entries, uint32_t nentries,
                              const uint8_t* d_ctrl /* may be NULL */, uint32_t ctrl_stride, uint32_t socket_v4,
                              neb_rx_packet* d_pk, neb_rx_source* d_src /* may be NULL */,
@@ -905,6 +906,96 @@ NEB_API int neb_rx_recv_plan_host(const neb_recv_entry* entries, uint32_t nentri
                                   uint32_t* pkt_entry /* may be NULL */, uint32_t max_packets,
                                   neb_udp_addr* from /* may be NULL */, uint32_t* entry_first,
                                   uint32_t* counts /* {npackets, nentries_done} */);
+/* ---- RX batch report: roaming runs, traffic marks, metrics, host work list ----------------------- */
+/* The side effects of readOutsidePackets (outside.go:30-189) and handleOutsideRelayPacket (:191-200)
+ * that are not the packet's bytes: messageMetrics.Rx / RxInvalid (message_metrics.go),
+ * handleHostRoaming, connectionManager.In / RelayUsed, the dispatch of the control types and
+ * maybeSendRecvError. One call behind neb_rx_open_wire_batch reduces a batch's statuses, headers,
+ * tunnels and sources to what the control plane acts on, so the caller loops over tunnels, not packets
+ * (DESIGN.md §3.17). */
+#define NEB_REPORT_RELAYED 1u   /* the packets came out of terminal relay packets (IsRelayed) */
+#define NEB_REPORT_NMETRICS 16
+#define NEB_METRIC_RX_HANDSHAKE 0      /* messages.rx.handshake_ixpsk0 */
+#define NEB_METRIC_RX_RECV_ERROR 1     /* messages.rx.recv_error */
+#define NEB_METRIC_RX_LIGHTHOUSE 2     /* messages.rx.lighthouse */
+#define NEB_METRIC_RX_TEST_REQUEST 3   /* messages.rx.test_request */
+#define NEB_METRIC_RX_TEST_RESPONSE 4  /* messages.rx.test_response */
+#define NEB_METRIC_RX_CLOSE_TUNNEL 5   /* messages.rx.close_tunnel */
+#define NEB_METRIC_RX_OTHER 6          /* messages.rx.other: Control, which newMessageMetrics gives no row */
+#define NEB_METRIC_RX_INVALID 7        /* messages.rx.invalid */
+#define NEB_METRIC_OPENED 8            /* packets with NEB_STATUS_OK */
+#define NEB_METRIC_OPENED_BYTES 9      /* ... and the sum of their wire lengths */
+#define NEB_METRIC_AUTH_FAILED 10      /* NEB_STATUS_AUTH_FAILED */
+#define NEB_METRIC_REPLAY 11           /* NEB_STATUS_REPLAY */
+#define NEB_METRIC_NO_TUNNEL 12        /* NEB_STATUS_BAD_KEY with key_id == NEB_KEYS_MIXED; 13..15: written as 0 */
+#define NEB_WORK_HANDSHAKE 1       /* handshakeManager.HandleIncoming (outside.go:84) */
+#define NEB_WORK_RECV_ERROR 2      /* handleRecvError (:88) */
+#define NEB_WORK_NESTED_RELAY 3    /* a Message/Relay inside a relay: one more level, the caller's */
+#define NEB_WORK_SEND_RECV_ERROR 4 /* maybeSendRecvError (:106): endpoint from from[], index from the header */
+#define NEB_WORK_LIGHTHOUSE 5      /* lhh.HandleRequest (:157) */
+#define NEB_WORK_TEST_REQUEST 6    /* the Test reply (:163-173) */
+#define NEB_WORK_CLOSE_TUNNEL 7    /* closeTunnel (:181) */
+#define NEB_WORK_CONTROL 8         /* relayManager.HandleControlMsg (:184) */
+typedef struct neb_rx_run {     /* consecutive authenticated packets of one tunnel from one source; 40 bytes */
+    uint64_t bytes;             /* sum of their wire lengths */
+    uint32_t key_id, packet /* the first one's index */, packets;
+    neb_udp_addr from;          /* all zero (family 0) when the packet has no source */
+} neb_rx_run;
+typedef struct neb_rx_relay_used { uint32_t index, packets; } neb_rx_relay_used;
+typedef struct neb_rx_work { uint32_t packet, kind; } neb_rx_work; /* kind: NEB_WORK_* */
+/* Per packet i < n: len is pk[i].len without NEB_RX_OWN_SOURCE; h, the 16 bytes at pk[i].off, is read
+ * only when len >= 16 (the header of an opened packet is intact: the open is in place behind it).
+ *   Source: from[pkt_entry[i]] with d_pkt_entry (the receive plan's outputs), else from[i]; all zero
+ *   when d_from is NULL, NEB_REPORT_RELAYED is set, or the index is NEB_RECV_NONE or >= nfrom (the
+ *   receive plan's padding never indexes from[]).
+ *   Metrics, in the gate's order (outside.go:32-79): rx.invalid counts status == NEB_STATUS_INVALID
+ *   with len > 1 (hole punches and padding are not counted). A packet with len >= 16, version 1, a
+ *   valid subtype and no NEB_RX_OWN_SOURCE (ignored with NEB_REPORT_RELAYED) counts Rx(type, subtype)
+ *   when its type is not Message, whatever its status ends as: no tunnel, len < 32, a failed tag, a
+ *   replay. Slots: NEB_METRIC_*; 13..15 are written as 0.
+ *   Authenticated: status == NEB_STATUS_OK (replays and failed tags return before outside.go:142).
+ *   These packets, and only these, enter runs and relay_used.
+ *   Runs: the authenticated packets sorted by (key_id, packet index); a run starts where key_id
+ *   changes or the 20-byte source differs from the previous packet's of that tunnel; runs are emitted
+ *   in that order, a tunnel's first run always (no remote[] snapshot is taken). counts[1] = ntunnels
+ *   is the number of distinct key_ids. The caller does connectionManager.In once per distinct key_id
+ *   and the unchanged handleHostRoaming(hostinfo, run.from) once per run whose from.family is not 0.
+ *   Leaving a repeat of the previous source out is exact: the second call with the same via is a
+ *   no-op or refused as the first was (DESIGN.md §3.17 names the one exception, a suppression that
+ *   expires between two packets of one batch).
+ *   relay_used: the distinct BE32(h[4:8]) of authenticated Message/Relay packets, ascending, each with
+ *   its packet count, for connectionManager.RelayUsed.
+ *   Work list, in arrival order: NEB_STATUS_NOT_MESSAGE gives HANDSHAKE (type 0), RECV_ERROR (type 2)
+ *   or, with NEB_REPORT_RELAYED, NESTED_RELAY (Message/Relay); NEB_STATUS_BAD_KEY with key_id ==
+ *   NEB_KEYS_MIXED and not relayed gives SEND_RECV_ERROR; NEB_STATUS_OK with type 3, 4/0, 5 or 6 gives
+ *   LIGHTHOUSE, TEST_REQUEST, CLOSE_TUNNEL or CONTROL. TestReply is a no-op there and is not listed.
+ *   A packet shorter than 16 bytes is never listed.
+ * Every output array holds n elements; runs, relay_used and work are written up to their counts and
+ * nothing beyond. n == 0: counts and metrics zeroed.
+ * Device pointers (d_runs and d_metrics 8-byte, the others 4-byte aligned); asynchronous on `stream`,
+ * no read-back, no synchronisation: it follows neb_rx_open_wire_batch on its stream directly. For a
+ * via batch it is called twice: for the outer packets, and for inner_pk / inner_status with
+ * NEB_REPORT_RELAYED.
+ * NEB_ERR_INVALID: e, d_counts or d_metrics NULL; with n != 0, d_pk, d_status, d_arena, d_runs,
+ * d_relay_used or d_work NULL; n >= 2^31; a misaligned pointer; an unknown bit in flags.
+ * Not part of the report: neb_relay_forward_batch rewrites the outer header of forwarded packets in
+ * place, so their original relay index is gone by the time statuses exist and RelayUsed for forwarded
+ * packets stays with the caller (runs and metrics remain valid for that call); handleHostRoaming's
+ * allow list and timers, and the connection manager itself; a CloseTunnel that takes effect on later
+ * packets of its own batch (table updates apply between batches); the TX side (connectionManager.Out). */
+NEB_API int neb_rx_report_batch(neb_engine* e, const neb_rx_packet* d_pk, const int32_t* d_status, uint32_t n,
+                                const uint8_t* d_arena, const neb_udp_addr* d_from /* may be NULL */,
+                                const uint32_t* d_pkt_entry /* may be NULL: d_from is per packet */, uint32_t nfrom,
+                                uint32_t flags, neb_rx_run* d_runs, neb_rx_relay_used* d_relay_used, neb_rx_work* d_work,
+                                uint64_t* d_metrics /* [NEB_REPORT_NMETRICS] */,
+                                uint32_t* d_counts /* {nruns, ntunnels, nrelay_used, nwork} */, void* stream);
+/* The same over host memory: the plain sequential loop, no engine, no GPU. Every packet of 16 bytes
+ * or more is checked against arena_len first (NEB_ERR_INVALID: nothing written). */
+NEB_API int neb_rx_report_batch_host(const neb_rx_packet* pk, const int32_t* status, uint32_t n, const uint8_t* arena,
+                                     size_t arena_len, const neb_udp_addr* from /* may be NULL */,
+                                     const uint32_t* pkt_entry /* may be NULL */, uint32_t nfrom, uint32_t flags,
+                                     neb_rx_run* runs, neb_rx_relay_used* relay_used, neb_rx_work* work,
+                                     uint64_t* metrics, uint32_t* counts);
 /* ---- TX resolve: parse, own-address gates and VPN address / route lookup for a TX batch -------- */
 /* The front half of consumeInsidePacket (inside.go:19-121) for a whole batch of TUN reads: newPacket
  * (outside.go:320-472, iputil/packet.go:349-395), the local-broadcast, self and multicast gates

@@ -144,6 +144,20 @@ RECV_ENTRY_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("seg_size", "<i4")
                              ("ctrl_len", "<u4")])
 assert RECV_ENTRY_DTYPE.itemsize == 48
 
+# neb_rx_report_batch (include/nebula_aead.h): a finished receive batch -> what the control plane acts on
+REPORT_RELAYED = 1
+REPORT_NMETRICS = 16
+(METRIC_RX_HANDSHAKE, METRIC_RX_RECV_ERROR, METRIC_RX_LIGHTHOUSE, METRIC_RX_TEST_REQUEST, METRIC_RX_TEST_RESPONSE,
+ METRIC_RX_CLOSE_TUNNEL, METRIC_RX_OTHER, METRIC_RX_INVALID, METRIC_OPENED, METRIC_OPENED_BYTES, METRIC_AUTH_FAILED,
+ METRIC_REPLAY, METRIC_NO_TUNNEL) = range(13)
+(WORK_HANDSHAKE, WORK_RECV_ERROR, WORK_NESTED_RELAY, WORK_SEND_RECV_ERROR, WORK_LIGHTHOUSE, WORK_TEST_REQUEST,
+ WORK_CLOSE_TUNNEL, WORK_CONTROL) = range(1, 9)
+RX_RUN_DTYPE = np.dtype([("bytes", "<u8"), ("key_id", "<u4"), ("packet", "<u4"), ("packets", "<u4"),
+                         ("from", UDP_ADDR_DTYPE)])
+RX_RELAY_USED_DTYPE = np.dtype([("index", "<u4"), ("packets", "<u4")])
+RX_WORK_DTYPE = np.dtype([("packet", "<u4"), ("kind", "<u4")])
+assert RX_RUN_DTYPE.itemsize == 40 and RX_RELAY_USED_DTYPE.itemsize == 8 and RX_WORK_DTYPE.itemsize == 8
+
 # Every symbol include/nebula_aead.h declares, with (restype, argtypes).
 _vp, _u8p, _sz, _u32, _u64, _i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
 SIGNATURES = {
@@ -224,6 +238,8 @@ SIGNATURES = {
     "neb_rx_resolve_batch_host": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
     "neb_rx_recv_plan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "neb_rx_recv_plan_host": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "neb_rx_report_batch": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "neb_rx_report_batch_host": (_i, [_vp, _vp, _u32, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "neb_tx_table_create": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "neb_tx_table_destroy": (_i, [_vp]),
     "neb_tx_table_update_hosts": (_i, [_vp, _vp, _u32, _vp, _u32, _vp]),

@@ -40,6 +40,7 @@
 #include "tx.hpp"
 #include "coalesce.hpp"
 #include "recv.hpp"
+#include "report.hpp"
 #include "send.hpp"
 #include "cipher.hpp"
 #include "engine_internal.hpp"
@@ -132,6 +133,14 @@ struct RecvSpace {
     neb::HipWorkspace<> dev;
     uint32_t n_cap = 0;
     neb::RecvWs ws{};
+    std::mutex mu;
+};
+
+// Device workspace of the RX batch report (report.hpp).
+struct ReportSpace {
+    neb::HipWorkspace<> dev;
+    uint32_t n_cap = 0;
+    neb::ReportWs ws{};
     std::mutex mu;
 };
 
@@ -249,6 +258,7 @@ struct neb_engine {
     CoSpace co;
     SendSpace send;
     RecvSpace recv;
+    ReportSpace report;
 
     // The host receive's zero-copy open (neb::RxStaging, window.cpp): a stream and mixed-key
     // workspace of its own, descriptors and statuses staged in pinned memory, one event.
@@ -1759,6 +1769,50 @@ NEB_API int neb_rx_recv_plan(neb_engine* e, const neb_recv_entry* d_entries, uin
     neb::RecvArgs a{d_entries, d_ctrl, d_pk, d_src, d_pkt_entry, d_from, d_entry_first, d_counts,
                     nentries, max_packets, ctrl_stride, socket_v4, sp.ws};
     HIP_TRY(neb_recv_run(&a, s));
+    HIP_TRY(sp.dev.end(s));
+    return NEB_OK;
+}
+
+// ---- RX batch report (report.hip) ------------------------------------------------------------------
+
+static hipError_t report_reserve(neb_engine* e, uint32_t n) {
+    ReportSpace& sp = e->report;
+    if (sp.dev.mem() && n <= sp.n_cap) return hipSuccess;
+    const uint32_t nc = std::max({n, sp.n_cap, 1024u});
+    size_t cub = 0;
+    const size_t bytes = neb_report_ws_bytes(nc, &cub);
+    sp.n_cap = 0;
+    hipError_t err = sp.dev.reserve(bytes);  // (laid out again whether it grew or not: the capacity changed)
+    if (err != hipSuccess) return err;
+    neb::report_ws_layout(nc, cub, sp.dev.mem(), &sp.ws);
+    sp.n_cap = nc;
+    return hipSuccess;
+}
+
+NEB_API int neb_rx_report_batch(neb_engine* e, const neb_rx_packet* d_pk, const int32_t* d_status, uint32_t n,
+                                const uint8_t* d_arena, const neb_udp_addr* d_from, const uint32_t* d_pkt_entry, uint32_t nfrom,
+                                uint32_t flags, neb_rx_run* d_runs, neb_rx_relay_used* d_relay_used, neb_rx_work* d_work,
+                                uint64_t* d_metrics, uint32_t* d_counts, void* stream) {
+    auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (!e || !d_metrics || !d_counts || n > 0x7FFFFFFFu || (flags & ~NEB_REPORT_RELAYED) ||
+        (n && (!d_pk || !d_status || !d_arena || !d_runs || !d_relay_used || !d_work)) ||
+        ((at(d_runs) | at(d_metrics)) & 7u) ||
+        ((at(d_pk) | at(d_status) | at(d_from) | at(d_pkt_entry) | at(d_relay_used) | at(d_work) | at(d_counts)) & 3u))
+        return NEB_ERR_INVALID;
+    DeviceGuard dg(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_metrics, 0, neb::kReportMetrics * sizeof(uint64_t), s));
+        HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint32_t), s));
+        return NEB_OK;
+    }
+    std::lock_guard<std::mutex> g(e->report.mu);
+    ReportSpace& sp = e->report;
+    HIP_TRY(report_reserve(e, n));
+    HIP_TRY(sp.dev.begin(s));
+    neb::ReportArgs a{d_pk, d_status, d_arena, d_from, d_pkt_entry, d_runs, d_relay_used, d_work, d_metrics, d_counts,
+                      n, nfrom, flags & NEB_REPORT_RELAYED, sp.ws};
+    HIP_TRY(neb_report_run(&a, s));
     HIP_TRY(sp.dev.end(s));
     return NEB_OK;
 }

@@ -8,7 +8,11 @@ neb_rx_open_wire_batch opened on the device there: receive() composes the two wi
 neb_rx_plain_from_wire in between.
 
 And the receive side before the resolve (neb_rx_recv_plan[_host]): ListenOut's split of a recvmmsg
-batch with UDP_GRO into wire packets (udp/udp_linux.go:237-331), recv_plan_host / recv_plan_device."""
+batch with UDP_GRO into wire packets (udp/udp_linux.go:237-331), recv_plan_host / recv_plan_device.
+
+And the bookkeeping after the open (neb_rx_report_batch[_host]): readOutsidePackets' side effects
+(outside.go:30-263) for a whole batch, reduced to runs per (tunnel, source), the relay indexes used,
+the host's work list and the metric counts, report_host / report_device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -168,6 +172,73 @@ def recv_plan_device(engine, d_entries, socket_v4: bool, d_packets, d_entry_firs
     L.check(rc, "neb_rx_recv_plan")
 
 
+class Report:
+    """One batch's report: runs (RX_RUN_DTYPE), relay_used (RX_RELAY_USED_DTYPE) and work (RX_WORK_DTYPE),
+    each cut to its count; metrics (REPORT_NMETRICS uint64, METRIC_*); ntunnels."""
+
+    def __init__(self, runs, relay_used, work, metrics, counts):
+        c = [int(x) for x in counts]
+        self.counts, self.ntunnels, self.metrics = c, c[1], metrics
+        self.runs, self.relay_used, self.work = runs[:c[0]], relay_used[:c[2]], work[:c[3]]
+
+
+def report_host(packets: np.ndarray, status: np.ndarray, arena: np.ndarray, frm: Optional[np.ndarray] = None,
+                pkt_entry: Optional[np.ndarray] = None, relayed: bool = False, arena_len: Optional[int] = None) -> Report:
+    """neb_rx_report_batch_host over a finished rx_open_wire_batch: packets (RX_PACKET_DTYPE, with the
+    resolve's key_id), their statuses, the arena, and the sources: frm (UDP_ADDR_DTYPE) per receive
+    entry with pkt_entry (the receive plan's outputs), per packet without it, or None."""
+    pk = np.ascontiguousarray(packets, dtype=L.RX_PACKET_DTYPE)
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    n = len(pk)
+    if len(st) != n:
+        raise ValueError("one status per packet")
+    if frm is not None:
+        frm = np.ascontiguousarray(frm, dtype=L.UDP_ADDR_DTYPE)
+    if pkt_entry is not None:
+        pkt_entry = np.ascontiguousarray(pkt_entry, dtype=np.uint32)
+        if len(pkt_entry) != n:
+            raise ValueError("one entry index per packet")
+    runs = np.zeros(max(n, 1), L.RX_RUN_DTYPE)
+    used = np.zeros(max(n, 1), L.RX_RELAY_USED_DTYPE)
+    work = np.zeros(max(n, 1), L.RX_WORK_DTYPE)
+    metrics = np.zeros(L.REPORT_NMETRICS, np.uint64)
+    counts = np.zeros(4, np.uint32)
+    opt = lambda a: None if a is None else _vp(a)  # noqa: E731
+    rc = L.lib().neb_rx_report_batch_host(_vp(pk), _vp(st), n, _vp(arena), arena.nbytes if arena_len is None else arena_len,
+                                          opt(frm), opt(pkt_entry), 0 if frm is None else len(frm),
+                                          L.REPORT_RELAYED if relayed else 0, _vp(runs), _vp(used), _vp(work), _vp(metrics),
+                                          _vp(counts))
+    L.check(rc, "neb_rx_report_batch_host")
+    return Report(runs, used, work, metrics, counts)
+
+
+def report_device(engine, d_packets, d_status, d_arena, d_runs, d_relay_used, d_work, d_metrics, d_counts, d_from=None,
+                  d_pkt_entry=None, relayed: bool = False, stream=None) -> None:
+    """neb_rx_report_batch over torch tensors on the engine's device: d_packets uint8 of RX_PACKET_DTYPE
+    records and d_status int32 as neb_rx_open_wire_batch left them, d_from uint8 of UDP_ADDR_DTYPE records
+    (per receive entry with d_pkt_entry int32 per packet, else per packet), d_runs uint8 of RX_RUN_DTYPE,
+    d_relay_used uint8 of RX_RELAY_USED_DTYPE and d_work uint8 of RX_WORK_DTYPE records, room for one per
+    packet each, d_metrics REPORT_NMETRICS int64, d_counts four int32 {nruns, ntunnels, nrelay_used,
+    nwork}. Only enqueues, behind the open on the same stream (torch's current one by default)."""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    n = d_packets.numel() // L.RX_PACKET_DTYPE.itemsize
+    for t, per in ((d_status, 1), (d_runs, L.RX_RUN_DTYPE.itemsize), (d_relay_used, L.RX_RELAY_USED_DTYPE.itemsize),
+                   (d_work, L.RX_WORK_DTYPE.itemsize), (d_pkt_entry, 1)):
+        if t is not None and t.numel() // per < n:
+            raise ValueError("an array is shorter than the batch")
+    if d_metrics.numel() * d_metrics.element_size() < 8 * L.REPORT_NMETRICS or d_counts.numel() * d_counts.element_size() < 16:
+        raise ValueError("d_metrics holds 16 uint64, d_counts four uint32")
+    nfrom = 0 if d_from is None else d_from.numel() // L.UDP_ADDR_DTYPE.itemsize
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = L.lib().neb_rx_report_batch(engine.handle, p(d_packets), p(d_status), n, p(d_arena), p(d_from), p(d_pkt_entry), nfrom,
+                                     L.REPORT_RELAYED if relayed else 0, p(d_runs), p(d_relay_used), p(d_work), p(d_metrics),
+                                     p(d_counts), C.c_void_p(s))
+    L.check(rc, "neb_rx_report_batch")
+
+
 class TunWrite:
     """One write to the TUN: the virtio_net_hdr fields and the bytes."""
 
@@ -252,4 +323,4 @@ def receive(engine, alg: int, windows: DeviceWindows, d_packets, d_arena, d_stat
 
 
 __all__ = ["MultiCoalescer", "TunWrite", "coalesce_batch_host", "coalesce_batch_device", "plain_from_wire_host",
-           "plain_from_wire_device", "inner_host", "inner_device", "receive", "recv_plan_host", "recv_plan_device"]
+           "plain_from_wire_device", "inner_host", "inner_device", "receive", "recv_plan_host", "recv_plan_device", "Report", "report_host", "report_device"]
