@@ -141,6 +141,28 @@ NEB_API int neb_engine_stats(const neb_engine* e, uint64_t stats[4]);
 /* Per-packet AES-256-GCM calls that arrived while every launch slot was busy ride together in one
  * launch (round 6): {such combined launches, calls they carried} since creation. */
 NEB_API int neb_engine_pkt_combined(const neb_engine* e, uint64_t out[2]);
+/* For tests: n <= 32 per-packet AES-256-GCM requests of one thread as one such combined launch, in
+ * the given order (request r rides in slot r of the batch), whatever else is in flight. `in` is the
+ * plaintext (seal; out takes in_len + 16 bytes) or the ciphertext and tag (open; out takes
+ * in_len - 16). key_id is a raw key slot and counter a raw counter: status[r] is the kernel's own
+ * NEB_STATUS_* of request r, and out is written as neb_encrypt_danger / neb_decrypt_danger write it
+ * (a failed open: zeros; any other failure: nothing). The batch is one of its own, taken and
+ * launched as the combiner does for concurrent calls, which it does not disturb; it counts in
+ * neb_engine_pkt_combined. n == 0 is NEB_OK. NEB_ERR_INVALID (nothing launched, nothing written):
+ * n > 32, a NULL argument, an open shorter than the tag, or a request the combiner would not take:
+ * with pay = ad_len rounded up to 16 it takes pay + in_len <= 2048 and pay + max(in_len, len + 16)
+ * <= 2112, len the payload's length without the tag. */
+typedef struct neb_pkt_req {
+    uint32_t key_id;
+    uint32_t reserved;
+    uint64_t counter;
+    const uint8_t* ad;
+    size_t ad_len;
+    const uint8_t* in;
+    size_t in_len;
+    uint8_t* out;
+} neb_pkt_req;
+NEB_API int neb_engine_pkt_launch(neb_engine* e, int open, const neb_pkt_req* req, uint32_t n, int32_t* status);
 /* Every entry point restores the calling thread's current HIP device before it returns. Streams
  * passed to the batch calls must stay alive until the work enqueued on them has completed. */
 /* Human-readable text of a return code. */

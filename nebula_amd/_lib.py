@@ -176,6 +176,7 @@ SIGNATURES = {
     "neb_cipher_create_multi": (_i, [_vp, _u32, _i, _u8p, _vp]),
     "neb_engine_stats": (_i, [_vp, _vp]),
     "neb_engine_pkt_combined": (_i, [_vp, _vp]),
+    "neb_engine_pkt_launch": (_i, [_vp, _i, _vp, _u32, _vp]),
     "neb_cipher_destroy": (_i, [_vp]),
     "neb_cipher_key_id": (_u32, [_vp]),
     "neb_cipher_alg": (_i, [_vp]),
@@ -274,6 +275,15 @@ class Shard(C.Structure):
     """neb_shard (include/nebula_aead.h): one engine's device-resident part of a sharded batch."""
     _fields_ = [("e", C.c_void_p), ("d_desc", C.c_void_p), ("n", C.c_uint32), ("d_arena", C.c_void_p),
                 ("d_status", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class PktReq(C.Structure):
+    """neb_pkt_req (include/nebula_aead.h): one request of neb_engine_pkt_launch."""
+    _fields_ = [("key_id", C.c_uint32), ("reserved", C.c_uint32), ("counter", C.c_uint64), ("ad", C.c_void_p),
+                ("ad_len", C.c_size_t), ("in_", C.c_void_p), ("in_len", C.c_size_t), ("out", C.c_void_p)]
+
+
+PKT_COMB_MAX = 32  # requests of one combined per-packet launch
 
 
 class QueueConfig(C.Structure):

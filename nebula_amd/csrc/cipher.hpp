@@ -7,16 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/nebula_aead.h"
-
-namespace neb {
-// A per-packet AES-256-GCM call whose AAD (padded to 16) + payload (+ tag) fit kOneBytes travels in
-// the kernel arguments (gcm_one_kernel); larger packets take the batch path.
-constexpr uint32_t kOneBytes = 2048;
-// Per-packet calls combined into one launch (engine.cpp PktComb, gcm_one_batch_kernel): up to kCombMax
-// requests, each in a slot of kCombSlot bytes: AAD | payload (+ tag), room for the tag a seal appends.
-constexpr uint32_t kCombMax = 32;
-constexpr uint32_t kCombSlot = kOneBytes + 64u;
-}  // namespace neb
+#include "host_common.hpp"  // kOneBytes, kCombMax, kCombSlot
 
 extern "C" {
 hipError_t neb_gcm_probe(void);

@@ -17,12 +17,9 @@
 #include <cstring>
 #include <cxxabi.h>
 #include <cstdlib>
-#include <climits>
-#include <linux/futex.h>
 #include <mutex>
 #include <new>
 #include <string>
-#include <sys/syscall.h>
 #include <thread>
 #include <type_traits>
 #include <unistd.h>
@@ -43,6 +40,7 @@
 #include "report.hpp"
 #include "send.hpp"
 #include "cipher.hpp"
+#include "comb_core.hpp"
 #include "engine_internal.hpp"
 
 // Device workspace of the mixed-key scheduler (sched.hpp). One per engine (and per queue batch,
@@ -61,8 +59,6 @@ constexpr size_t kStageMin = 1 << 16;
 using neb::BatchLaunch;
 using neb::DevBuf;
 using neb::PinnedBuf;
-using neb::kCombMax;  // cipher.hpp
-using neb::kCombSlot;
 using neb::kPipeChunkPkts;  // pipe_core.hpp: the staged host pipeline's chunk plan and spans
 using neb::kPipeSlots;
 
@@ -170,52 +166,35 @@ struct PktPool {
     std::deque<PktWaiter*> waiters;
     std::atomic<uint64_t> calls{0}, waits{0};
 };
-// Per-packet AES-256-GCM calls that arrive while kPktSlots launches are in flight (round 6): they join
-// one pinned batch of up to kCombMax requests, which its first request (the leader) launches as a
-// whole (gcm_one_batch_kernel) as soon as one of the launches ahead completes; the leader polls
-// every status, wakes the others, and each copies its own result out. A call that finds a launch
-// free launches alone as before (the packet in the kernel arguments), so up to kPktSlots threads see
-// no change; past that the batches grow with the offered load.
-constexpr size_t kCombDescOff = 0, kCombStatusOff = 2u << 10, kCombSlotsOff = 4u << 10;  // 2 KiB for each
-static_assert(kCombMax * sizeof(neb_desc) <= kCombStatusOff && kCombMax * 4u <= kCombSlotsOff - kCombStatusOff, "");
-constexpr size_t kCombBytes = kCombSlotsOff + (size_t)kCombMax * kCombSlot;
-struct CombBatch {
-    PinnedBuf<> h;   // mapped: descriptors | statuses | slots
-    uint32_t n = 0;  // requests joined
-    int alg = 0, open = 0;
-    bool launched = false;  // (PktComb::mu)
-    hipStream_t stream = nullptr;
-    std::atomic<uint32_t> left{0};  // requests whose owner has not copied its result out yet
-    // The leader saw every status: the owners may copy out. A futex word of the batch's own, so the
-    // owners wake without queueing on a mutex (64 threads on a 16-CPU share: p99 23 ms when they
-    // woke through the engine's combiner mutex).
-    std::atomic<uint32_t> done{0};
-    bool failed = false;  // written before done's release
-    void finish(bool f) {
-        failed = f;
-        done.store(1, std::memory_order_release);
-        syscall(SYS_futex, reinterpret_cast<uint32_t*>(&done), FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0);
-    }
-    bool wait() {  // the failure flag
-        while (!done.load(std::memory_order_acquire))
-            syscall(SYS_futex, reinterpret_cast<uint32_t*>(&done), FUTEX_WAIT_PRIVATE, 0, nullptr, nullptr, 0);
-        return failed;
-    }
-    neb_desc* desc() const { return reinterpret_cast<neb_desc*>(h + kCombDescOff); }
-    int32_t* status() const { return reinterpret_cast<int32_t*>(h + kCombStatusOff); }
-    uint8_t* slots() const { return h + kCombSlotsOff; }
+// Per-packet AES-256-GCM calls that arrive while kPktSlots launches are in flight (round 6) ride
+// together in one launch: the combiner (comb_core.hpp) over HIP. A call alone is one_packet_solo on a
+// slot of the per-packet pool; a batch's buffer is pinned, mapped memory, its launch
+// gcm_one_batch_kernel on the pool's streams in turn, its completion handle that stream.
+struct HipComb {
+    using Buf = PinnedBuf<>;
+    using Token = hipStream_t;
+    struct Guard {
+        DeviceGuard g;
+        explicit Guard(HipComb& d);
+    };
+    neb_engine* e = nullptr;
+    bool reserve(Buf& h, size_t bytes);
+    int solo(const neb::CombReq& q, int32_t* st);
+    bool launch(int open, const neb_desc* desc, int32_t* status, uint8_t* slots, uint32_t n, uint32_t turn, Token& s);
+    bool poll(Token&, const int32_t* p);
+    bool sync(Token& s);
+    void count(uint32_t n);
 };
-struct PktComb {
-    std::mutex mu;
-    uint32_t inflight = 0;          // launches (alone or combined) not yet complete, at most pkt_inflight()
-    uint32_t solo = 0;              // of them alone (each holds a pool slot), at most kPktSlots
-    std::condition_variable launch_cv;  // a launch completed (the leaders of gathering batches wait)
-    CombBatch* open[2][2] = {};     // accepting requests: [AES-GCM / ChaCha20][seal / open]
-    std::vector<CombBatch*> free_;
-    std::vector<std::unique_ptr<CombBatch>> all;
-    uint32_t next = 0;              // the per-packet pool's streams carry the combined launches in turn
-    std::atomic<uint64_t> launches{0}, combined{0};
-};
+// NEB_PKT_INFLIGHT: launches in flight before calls combine (A/B), default kPktSlots; read once
+static uint32_t pkt_inflight() {
+    static const uint32_t v = [] {
+        const char* s = std::getenv("NEB_PKT_INFLIGHT");
+        const int x = s ? std::atoi(s) : (int)kPktSlots;
+        return (uint32_t)std::min(std::max(x, 1), 64);
+    }();
+    return v;
+}
+using PktComb = neb::CombCore<HipComb>;
 struct KeyUse {
     hipStream_t s;
     neb::Event ev;
@@ -237,7 +216,7 @@ struct neb_engine {
     uint64_t installs = 0;
 
     PktPool pkt;  // per-packet calls and key installs
-    PktComb comb; // per-packet calls combined into one launch
+    PktComb comb{pkt_inflight(), kPktSlots};  // per-packet calls combined into one launch
 
     // Asynchronous batches still queued when a key is destroyed: per key slot, the last
     // single-key batch the engine launched on each stream, and the last mixed-key batch per
@@ -472,6 +451,7 @@ NEB_API int neb_engine_create(int device, uint32_t max_keys, neb_engine** out) {
     neb_engine* e = new (std::nothrow) neb_engine();
     if (!e) return NEB_ERR_INVALID;
     e->device = device;
+    e->comb.dev.e = e;
     e->cu_count = cus;
     e->max_keys = max_keys;
     e->slot_alg.assign(max_keys, 0);
@@ -877,28 +857,19 @@ static bool poll_status(const int32_t* p, int32_t* st, int us = kPollUs) {
     }
 }
 
-// A per-packet call's result from its pool slot into the caller's buffer, by status: a sealed or
-// opened packet is copied; a failed open leaves zeros (the kernel's in-place zeroing, written here
-// so the slot is never read); any other status (no key, exhausted counter) writes nothing, as the
-// reference returns before touching out (aesgcm.go:28-30). The slot's bytes are read only when the
-// kernel wrote them: slots are shared by every thread and cipher of the engine, so anything else
-// there is another call's packet.
-static void copy_result(int open, int32_t st, uint8_t* dst, const uint8_t* slot, size_t pay_len) {
-    const size_t out_len = open ? pay_len : pay_len + 16;
-    if (!out_len) return;
-    if (st == NEB_STATUS_OK)
-        std::memcpy(dst, slot, out_len);
-    else if (open && st == NEB_STATUS_AUTH_FAILED)
-        std::memset(dst, 0, out_len);
-}
+using neb::copy_result;  // comb_core.hpp
 
 // One packet through the device, on a slot of the engine's per-packet pool (PktPool): the packet is
 // copied into the slot's pinned, mapped buffer ([desc | status | aad | payload (+tag)]), the batch
 // kernel seals or opens it there in place (zero-copy: no DMA either way) and the result is copied
 // out. Up to kPktSlots calls run side by side; later ones wait their turn in FIFO order.
-static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad_len, const uint8_t* in,
-                           size_t in_len, size_t pay_len, uint64_t n, uint8_t* dst, int32_t* st_out) {
-    neb_engine* e = c->e;
+static int one_packet_solo(neb_engine* e, const neb::CombReq& q, int32_t* st_out) {
+    const int alg = q.alg, open = q.open;
+    const uint32_t key_id = q.key_id;
+    const uint8_t *ad = q.ad, *in = q.in;
+    const size_t ad_len = q.ad_len, in_len = q.in_len, pay_len = q.pay_len;
+    const uint64_t n = q.n;
+    uint8_t* dst = q.dst;
     const size_t o_desc = 0, o_status = 64, o_aad = 128;
     const size_t o_pay = align_up(o_aad + ad_len, 16);
     const size_t total = o_pay + pay_len + 16;
@@ -909,9 +880,9 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
     // The packet's bytes travel in the kernel's arguments and only the result comes back through
     // the slot (aes_gcm.hip gcm_one_kernel, chacha_poly.hip chacha_one_kernel).
     *(int32_t*)(h + o_status) = -1;
-    auto* fn = c->alg == NEB_ALG_AESGCM ? neb_gcm_one : neb_chacha_one;
+    auto* fn = alg == NEB_ALG_AESGCM ? neb_gcm_one : neb_chacha_one;
     hipError_t err = fn(open, ad, (uint32_t)ad_len, in, (uint32_t)in_len, (uint32_t)pay_len, n, h + o_pay,
-                        (int32_t*)(h + o_status), e->d_keys, e->max_keys, c->key_id, sl->stream);
+                        (int32_t*)(h + o_status), e->d_keys, e->max_keys, key_id, sl->stream);
     if (err == hipSuccess) {
         // the kernel publishes the status last, behind a system-scope release of the result
         // (device_common.hpp one_publish_status): poll it, and wait for the stream only if it
@@ -942,13 +913,13 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
     d.counter = n;
     d.len = (uint32_t)pay_len;
     d.aad_len = (uint32_t)ad_len;
-    d.key_id = c->key_id;
+    d.key_id = key_id;
     std::memcpy(h + o_desc, &d, sizeof d);
     *(int32_t*)(h + o_status) = -1;
     if (ad_len) std::memcpy(h + o_aad, ad, ad_len);
     if (in_len) std::memcpy(h + o_pay, in, in_len);
-    err = launch_batch(e, {.alg = c->alg, .open = open, .desc = (const neb_desc*)(h + o_desc), .n = 1, .arena = h + o_aad,
-                           .status = (int32_t*)(h + o_status), .key_hint = c->key_id, .stream = sl->stream});
+    err = launch_batch(e, {.alg = alg, .open = open, .desc = (const neb_desc*)(h + o_desc), .n = 1, .arena = h + o_aad,
+                           .status = (int32_t*)(h + o_status), .key_hint = key_id, .stream = sl->stream});
     if (err == hipSuccess) err = hipStreamSynchronize(sl->stream);
     if (err != hipSuccess) {
         set_error("one_packet", err);
@@ -959,131 +930,78 @@ static int one_packet_solo(neb_cipher* c, int open, const uint8_t* ad, size_t ad
     return NEB_OK;
 }
 
-// A per-packet call through the engine's combiner (PktComb): alone while a launch slot is free
-// (one_packet_solo: the packet in the kernel arguments), else as a request of the batch the next
-// completed launch frees a slot for. AES-256-GCM only (the ChaCha20-Poly1305 batch kernel's statuses carry no
-// release of the payload before them, so its calls stay alone).
+// The combiner's device (comb_core.hpp) on HIP.
+HipComb::Guard::Guard(HipComb& d) : g(d.e->device) {}
+bool HipComb::reserve(Buf& h, size_t bytes) {
+    if (h.reserve(bytes) == hipSuccess) return true;
+    set_error("pinned memory (per-packet batch)", hipErrorOutOfMemory);
+    return false;
+}
+int HipComb::solo(const neb::CombReq& q, int32_t* st) { return one_packet_solo(e, q, st); }
+bool HipComb::launch(int open, const neb_desc* desc, int32_t* status, uint8_t* slots, uint32_t n, uint32_t turn,
+                     Token& s) {
+    s = e->pkt.slot[turn % kPktSlots].stream;  // the per-packet pool's streams carry the combined launches in turn
+    const hipError_t err = neb_gcm_one_batch(open, desc, status, slots, n, e->d_keys, e->max_keys, s);
+    if (err != hipSuccess) set_error("per-packet batch launch", err);
+    return err == hipSuccess;
+}
+bool HipComb::poll(Token&, const int32_t* p) {
+    int32_t v;
+    return poll_status(p, &v);
+}
+bool HipComb::sync(Token& s) {
+    const hipError_t err = hipStreamSynchronize(s);
+    if (err != hipSuccess) set_error("per-packet batch launch", err);
+    return err == hipSuccess;
+}
+void HipComb::count(uint32_t n) { e->pkt.calls.fetch_add(n, std::memory_order_relaxed); }  // (neb_engine_stats)
+
+// A per-packet call through the engine's combiner (PktComb, comb_core.hpp): alone while a launch
+// slot is free (one_packet_solo: the packet in the kernel arguments), else as a request of the
+// batch the next completed launch frees a slot for. AES-256-GCM only (the ChaCha20-Poly1305 batch
+// kernel's statuses carry no release of the payload before them, so its calls stay alone).
 static int one_packet(neb_cipher* c, int open, const uint8_t* ad, size_t ad_len, const uint8_t* in, size_t in_len,
                       size_t pay_len, uint64_t n, uint8_t* dst, int32_t* st_out) {
-    neb_engine* e = c->e;
-    const size_t pay = align_up(ad_len, 16);
-    if (c->alg != NEB_ALG_AESGCM || pay + std::max(in_len, pay_len + 16) > kCombSlot || pay + in_len > neb::kOneBytes)
-        return one_packet_solo(c, open, ad, ad_len, in, in_len, pay_len, n, dst, st_out);
-    static const uint32_t max_inflight = [] {  // NEB_PKT_INFLIGHT: launches in flight (A/B), default 4
-        const char* v = std::getenv("NEB_PKT_INFLIGHT");
-        const int x = v ? std::atoi(v) : (int)kPktSlots;
-        return (uint32_t)std::min(std::max(x, 1), 64);
-    }();
-    PktComb& cb = e->comb;
-    std::unique_lock<std::mutex> lk(cb.mu);
-    CombBatch*& ob = cb.open[0][open ? 1 : 0];
-    // Alone while a launch and a pool slot are free and no batch is gathering (each alone call
-    // holds a pool slot; only these take slots here).
-    if (cb.inflight < max_inflight && cb.solo < kPktSlots && !ob) {
-        cb.inflight++;
-        cb.solo++;
-        lk.unlock();
-        const int rc = one_packet_solo(c, open, ad, ad_len, in, in_len, pay_len, n, dst, st_out);
-        lk.lock();
-        cb.inflight--;
-        cb.solo--;
-        lk.unlock();
-        cb.launch_cv.notify_all();
-        return rc;
-    }
-    DeviceGuard dg(e->device);
-    if (!ob) {
-        if (cb.free_.empty()) {
-            std::unique_ptr<CombBatch> nb(new (std::nothrow) CombBatch);
-            if (!nb) return NEB_ERR_INVALID;
-            if (nb->h.reserve(kCombBytes) != hipSuccess) {
-                set_error("pinned memory (per-packet batch)", hipErrorOutOfMemory);
-                return NEB_ERR_HIP;
-            }
-            cb.free_.push_back(nb.get());
-            cb.all.push_back(std::move(nb));
-        }
-        ob = cb.free_.back();
-        cb.free_.pop_back();
-        ob->n = 0;
-        ob->launched = false;
-        ob->failed = false;
-        ob->done.store(0, std::memory_order_relaxed);
-        ob->alg = c->alg;
-        ob->open = open;
-    }
-    CombBatch* b = ob;
-    const uint32_t i = b->n++;
-    if (b->n == kCombMax) ob = nullptr;  // full: the next call starts another
-    uint8_t* slot = b->slots() + (size_t)i * kCombSlot;
-    if (ad_len) std::memcpy(slot, ad, ad_len);
-    if (in_len) std::memcpy(slot + pay, in, in_len);
-    neb_desc& d = b->desc()[i];
-    d = neb_desc{};
-    d.aad_off = (uint64_t)i * kCombSlot;
-    d.src_off = d.dst_off = d.aad_off + pay;  // in place in the slot
-    d.counter = n;
-    d.len = (uint32_t)pay_len;
-    d.aad_len = (uint32_t)ad_len;
-    d.key_id = c->key_id;
-    __atomic_store_n(b->status() + i, -1, __ATOMIC_RELAXED);
-    // The batch's first request leads it: it waits until a launch completes, launches the batch as
-    // it stands then (every joined request is filled: joiners fill under the mutex), polls every
-    // status and wakes the others. Under load the batch gathers for as long as the launches ahead
-    // of it run, so its size follows the offered load; one thread spins per launch, the rest sleep
-    // (64 threads spinning on a 16-CPU share starved the launches: p99 37 ms).
-    if (i == 0) {
-        cb.launch_cv.wait(lk, [&] { return cb.inflight < max_inflight; });
-        cb.inflight++;
-        if (ob == b) ob = nullptr;
-        b->launched = true;
-        b->left.store(b->n, std::memory_order_relaxed);
-        b->stream = e->pkt.slot[cb.next++ % kPktSlots].stream;
-        const uint32_t cnt = b->n;
-        e->pkt.calls.fetch_add(cnt, std::memory_order_relaxed);  // (neb_engine_stats: per-packet calls)
-        lk.unlock();
-        hipError_t err = neb_gcm_one_batch(open, b->desc(), b->status(), b->slots(), cnt, e->d_keys, e->max_keys,
-                                           b->stream);
-        cb.launches.fetch_add(1, std::memory_order_relaxed);
-        cb.combined.fetch_add(cnt, std::memory_order_relaxed);
-        if (err == hipSuccess) {
-            bool slow = false;
-            for (uint32_t k = 0; k < cnt && !slow; k++) {
-                int32_t v;
-                slow = !poll_status(b->status() + k, &v);
-            }
-            if (slow) err = hipStreamSynchronize(b->stream);  // a slow device: the stream says when
-        }
-        if (err != hipSuccess) set_error("per-packet batch launch", err);
-        lk.lock();
-        cb.inflight--;
-        lk.unlock();
-        cb.launch_cv.notify_all();
-        b->finish(err != hipSuccess);
-    } else {
-        lk.unlock();
-    }
-    // (the owners sleep rather than poll their own status words: 8 spinners measured 317-336 k /
-    // 363-387 k calls/s at 16 / 32 threads against 338-341 k / 530-542 k sleeping)
-    const bool failed = b->wait();
-    const int32_t st = failed ? -1 : __atomic_load_n(b->status() + i, __ATOMIC_ACQUIRE);
-    if (st != -1) copy_result(open, st, dst, slot + pay, pay_len);
-    if (b->left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
-        lk.lock();
-        cb.free_.push_back(b);
-        lk.unlock();
-    }
-    if (st == -1) return NEB_ERR_HIP;
-    *st_out = st;
-    return NEB_OK;
+    neb::CombReq q;
+    q.alg = c->alg;
+    q.open = open;
+    q.key_id = c->key_id;
+    q.n = n;
+    q.ad = ad;
+    q.ad_len = ad_len;
+    q.in = in;
+    q.in_len = in_len;
+    q.pay_len = pay_len;
+    q.dst = dst;
+    return c->e->comb.call(q, st_out);
 }
 
 // Per-packet calls combined into shared launches: {launches of combined batches, calls they carried}
 NEB_API int neb_engine_pkt_combined(const neb_engine* e, uint64_t out[2]) {
     if (!e || !out) return NEB_ERR_INVALID;
-    out[0] = e->comb.launches.load(std::memory_order_relaxed);
-    out[1] = e->comb.combined.load(std::memory_order_relaxed);
+    e->comb.counters(out);
     return NEB_OK;
+}
+
+// For tests: req[0..n) as one combined launch, request r in slot r (CombCore::run).
+NEB_API int neb_engine_pkt_launch(neb_engine* e, int open, const neb_pkt_req* req, uint32_t n, int32_t* status) {
+    if (!e || n > neb::kCombMax || (n && (!req || !status))) return NEB_ERR_INVALID;
+    neb::CombReq q[neb::kCombMax];
+    for (uint32_t r = 0; r < n; r++) {
+        const neb_pkt_req& p = req[r];
+        if ((!p.ad && p.ad_len) || (!p.in && p.in_len) || !p.out || (open && p.in_len < NEB_OVERHEAD)) return NEB_ERR_INVALID;
+        q[r].alg = NEB_ALG_AESGCM;
+        q[r].open = open ? 1 : 0;
+        q[r].key_id = p.key_id;
+        q[r].n = p.counter;
+        q[r].ad = p.ad;
+        q[r].ad_len = p.ad_len;
+        q[r].in = p.in;
+        q[r].in_len = p.in_len;
+        q[r].pay_len = open ? p.in_len - NEB_OVERHEAD : p.in_len;
+        q[r].dst = p.out;
+    }
+    return e->comb.run(open ? 1 : 0, q, n, status);
 }
 
 NEB_API int neb_encrypt_danger(neb_cipher* c, uint8_t* out, size_t out_len, size_t out_cap, const uint8_t* ad,

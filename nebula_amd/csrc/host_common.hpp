@@ -6,6 +6,17 @@
 
 #include "../../include/nebula_aead.h"
 
+namespace neb {
+// The sizes both sides of the per-packet path agree on (the kernels take them through cipher.hpp).
+// A per-packet AES-256-GCM call whose AAD (padded to 16) + payload (+ tag) fit kOneBytes travels in
+// the kernel arguments (gcm_one_kernel); larger packets take the batch path.
+constexpr uint32_t kOneBytes = 2048;
+// Per-packet calls combined into one launch (comb_core.hpp, gcm_one_batch_kernel): up to kCombMax
+// requests, each in a slot of kCombSlot bytes: AAD | payload (+ tag), room for the tag a seal appends.
+constexpr uint32_t kCombMax = 32;
+constexpr uint32_t kCombSlot = kOneBytes + 64u;
+}  // namespace neb
+
 // [off, off + len) lies inside [0, cap), written so that no sum can wrap around 2^64.
 inline bool span_in(uint64_t off, uint64_t len, uint64_t cap) { return off <= cap && len <= cap - off; }
 

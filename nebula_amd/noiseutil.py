@@ -117,6 +117,25 @@ class Engine:
         return {"pkt_slots": v[0], "pkt_calls": v[1], "pkt_waits": v[2], "installs": v[3],
                 "pkt_combined_launches": c[0], "pkt_combined_calls": c[1]}
 
+    def pkt_launch(self, open_: bool, reqs, status):
+        """neb_engine_pkt_launch (for tests): reqs = [(key_id, counter, ad, in_, out)], each of ad,
+        in_ and out a contiguous uint8 numpy array (out is written in place; an empty ad or in_ may
+        be None), as one combined per-packet launch, request r in slot r. `status` is an int32
+        array of len(reqs). Returns the call's return code; nothing is raised."""
+        import numpy as np
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        for _, _, ad, in_, out in reqs:
+            assert all(a is None or (a.dtype == np.uint8 and a.flags.c_contiguous) for a in (ad, in_, out))
+        assert status.dtype == np.int32 and len(status) >= len(reqs)
+        arr = (L.PktReq * max(len(reqs), 1))()
+        for r, (key_id, counter, ad, in_, out) in enumerate(reqs):
+            arr[r] = L.PktReq(key_id, 0, counter, ptr(ad), 0 if ad is None else len(ad), ptr(in_),
+                              0 if in_ is None else len(in_), ptr(out))
+        return L.lib().neb_engine_pkt_launch(self.handle, 1 if open_ else 0, arr, len(reqs), status.ctypes.data)
+
     def close(self) -> None:
         if self.handle:
             L.lib().neb_engine_destroy(self.handle)

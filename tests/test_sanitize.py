@@ -3,7 +3,9 @@ builds window_core.hpp (replay window, exact receive rounds, thread pool) and qu
 submission queue, on a CPU device running the oracle) and workspace.hpp (the device workspaces'
 event and stream protocol, on a fake device that logs the calls) and hip_owned.hpp (the owned
 buffers' growth, moves and release, on such a fake too) and table_mirror.hpp (the lookup tables'
-two device images, staging and events, on such a fake too) and pipe_core.hpp (the staged host
+two device images, staging and events, on such a fake too) and comb_core.hpp (the per-packet
+combiner's leader/joiner protocol, on a fake device whose launches the test holds and releases)
+and pipe_core.hpp (the staged host
 pipeline's chunk plan, chunk spans and overlap test, against brute force) with ASan+UBSan and with
 TSan and runs them; the first two also check their results against the packet-by-packet receive /
 the oracle."""
@@ -26,3 +28,4 @@ def test_sanitizer_builds_run_clean():
     assert r.stdout.count("pipe_test: ok") == 2, r.stdout
     assert r.stdout.count("owned_test: ok") == 2, r.stdout
     assert r.stdout.count("mirror_test: ok") == 2, r.stdout
+    assert r.stdout.count("comb_test: ok") == 2, r.stdout
