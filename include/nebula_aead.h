@@ -1239,6 +1239,121 @@ NEB_API int neb_rx_inner_batch_host(const neb_peer_table* t, const neb_rx_packet
                                     const uint64_t* epoch, uint32_t nepoch, uint32_t n, const uint8_t* arena,
                                     size_t arena_len, neb_plain_packet* plain, neb_fw_packet* fw,
                                     int32_t* inner_status);
+/* ---- conntrack: firewall.Conntrack.Conns for TX and RX batches --------------------------------- */
+/* firewall.Drop asks inConns before it looks at any rule (firewall.go:459-478), and an established
+ * flow never reaches the rules. The map[firewall.Packet]*conn lives in a table beside the others and
+ * answers the three operations the reference does on it: inConns (lookup), addConn (add) and evict
+ * (firewall.go:505-630). Rule evaluation and the timer wheel stay with the caller: after a lookup
+ * only the packets of new flows and of flows added under older rules leave the device, as a compact
+ * work list; established flows go straight on to neb_rx_coalesce_batch or neb_tx_seal_batch.
+ * The key is LocalAddr, RemoteAddr, LocalPort, RemotePort, Protocol and Fragment, taken from a
+ * neb_fw_packet: local_addr, remote_addr, local_port, remote_port, protocol, family and the
+ * NEB_FW_FRAGMENT bit of flags. For family 4 only the first 4 address bytes count (bytes 4..15 of the
+ * input are not trusted); a 4-in-6 address never equals its IPv4 form, as with netip. ip_hdr_len,
+ * gateway, the other flag bits and the reserved fields are not part of the key. The value is Expires
+ * (ns of the caller's monotonic clock), incoming and rulesVersion.
+ * Concurrency: add, evict, compact and set_rules_version on one table are serialised by the caller
+ * (one stream, or waits); lookups may run on any stream at the same time as an add or an evict, and a
+ * key that stays in the table never misses. Nothing may run during neb_conntrack_compact. */
+#define NEB_STATUS_FW_HELD 18 /* the conntrack lookup held the packet for the caller's rules */
+#define NEB_CT_NONE 0         /* verdict: input status != NEB_STATUS_OK, not looked up */
+#define NEB_CT_HIT 1          /* established: Expires refreshed */
+#define NEB_CT_MISS 2         /* no entry: the caller's rules decide */
+#define NEB_CT_STALE 3        /* an entry of another rulesVersion, untouched (firewall.go:527-560) */
+#define NEB_CT_INCOMING 0x80  /* or-ed into a STALE verdict: the entry's incoming */
+#define NEB_CT_NEW 1          /* add: inserted; the caller adds the key to its timer wheel */
+#define NEB_CT_EXISTING 2     /* add: the entry's three fields overwritten; no wheel add */
+#define NEB_CT_DUP 3          /* add: another copy of the key in this batch answered NEW or EXISTING */
+#define NEB_CT_FULL 4         /* add: refused, nothing changed; slot is NEB_CT_NO_SLOT */
+#define NEB_CT_NO_SLOT 0xFFFFFFFFu
+typedef struct neb_ct_work { /* one packet for the caller's rules. 16-byte aligned. */
+    uint32_t packet;         /* index in the batch */
+    uint32_t verdict;        /* NEB_CT_MISS, or NEB_CT_STALE [| NEB_CT_INCOMING] */
+    neb_fw_packet fw;        /* the packet's input record, as given */
+    uint8_t reserved[8];     /* 0 */
+} neb_ct_work;
+typedef struct neb_ct_result {
+    uint32_t code; /* NEB_CT_NEW, _EXISTING, _DUP, _FULL */
+    uint32_t slot; /* where the entry is (every copy of a key reports the same) */
+} neb_ct_result;
+typedef struct neb_conntrack neb_conntrack;
+
+/* A table of at most `capacity` live entries (1..2^22; fixed: a documented departure, the reference's
+ * map has no bound, firewall.go:40). Its slots, 64 bytes each, number the power of two >= 2 x
+ * capacity. seed keys the hash, so which flows share a chain is the owner's secret (and a test's
+ * choice). tcp_ns, udp_ns, default_ns: the three timeouts (firewall.go:562-569). max_batch (>= 1):
+ * the largest n of a batch call; the lookup's device workspace is sized for it here. The rules
+ * version starts at 0. e == NULL: a host-only table (the _host calls only), the same image in host
+ * memory under the same rules; otherwise the image lives in e's device memory only (the device
+ * changes it, so there is no host copy) and only the device calls work. */
+NEB_API int neb_conntrack_create(neb_engine* e, uint32_t capacity, uint64_t seed, uint64_t tcp_ns, uint64_t udp_ns,
+                                 uint64_t default_ns, uint32_t max_batch, neb_conntrack** out);
+/* No call on the table may be in progress; waits for the device work the table has enqueued. */
+NEB_API int neb_conntrack_destroy(neb_conntrack* t);
+/* f.rulesVersion after a reload: calls enqueued after this returns use v. */
+NEB_API int neb_conntrack_set_rules_version(neb_conntrack* t, uint16_t v);
+/* inConns per packet i (the localCache argument is a per-routine shortcut with no semantics: no
+ * counterpart). status[i] != NEB_STATUS_OK: verdict NEB_CT_NONE, not looked up, nothing else written
+ * for it. Otherwise: key absent -> NEB_CT_MISS; present with another rulesVersion -> NEB_CT_STALE
+ * [| NEB_CT_INCOMING], the entry untouched: the caller re-matches its rules in that direction and
+ * then adds the key again with that incoming, or evicts it with force; else NEB_CT_HIT and Expires =
+ * max(Expires, now_ns + timeout(protocol)). now_ns is one reading of a monotonic clock per call,
+ * under which the max is the reference's overwrite. An entry past its Expires that nobody has
+ * evicted still hits and is refreshed, as in the reference: the table expires nothing by itself.
+ * Holding: with d_plain and / or d_tx given, every looked-up packet that is not a HIT gets
+ * NEB_PLAIN_SKIP or-ed into d_plain[i].flags, d_tx[i].tunnel = NEB_TX_NO_TUNNEL and d_status[i] =
+ * NEB_STATUS_FW_HELD, so the coalescer or the seal that follows on the stream passes the hits on only.
+ * With both NULL, d_status is only read.
+ * Work list: the MISS and STALE packets in ascending packet order, at most work_cap of them (d_work
+ * may be NULL with work_cap == 0). d_counts = {hits, misses, stales, work entries in total, also
+ * beyond work_cap}. All packets of one flow in one batch get the same verdict.
+ * d_fw, d_work and d_plain are 16-byte aligned. n == 0 returns NEB_OK and enqueues nothing.
+ * NEB_ERR_INVALID (nothing launched): n > max_batch, a misaligned or missing array, a host-only
+ * table, a table of another engine. */
+NEB_API int neb_conntrack_lookup_batch(neb_engine* e, neb_conntrack* t, const neb_fw_packet* d_fw, int32_t* d_status,
+                                       uint32_t n, uint64_t now_ns, uint8_t* d_verdict, neb_plain_packet* d_plain,
+                                       neb_tx_packet* d_tx, neb_ct_work* d_work, uint32_t work_cap, uint32_t* d_counts,
+                                       void* stream);
+/* The same over host memory, on a host-only table; any alignment. */
+NEB_API int neb_conntrack_lookup_batch_host(neb_conntrack* t, const neb_fw_packet* fw, int32_t* status, uint32_t n,
+                                            uint64_t now_ns, uint8_t* verdict, neb_plain_packet* plain, neb_tx_packet* tx,
+                                            neb_ct_work* work, uint32_t work_cap, uint32_t* counts);
+/* addConn per key i with incoming[i] != 0 as its direction: absent -> {now_ns + timeout, incoming,
+ * the current rulesVersion} inserted, NEB_CT_NEW; present -> the three fields overwritten,
+ * NEB_CT_EXISTING. Of several copies of one key in a batch exactly one answers NEW or EXISTING, the
+ * others NEB_CT_DUP, all with the same slot, and the stored incoming is that of the highest index, as
+ * sequential addConn calls would leave it. An add that would take the live count past capacity, or
+ * that finds no empty slot (tombstones: compact), answers NEB_CT_FULL, as do all copies of its key;
+ * the flow is then untracked and takes the rules path every time. Which of a batch's new keys are
+ * refused is unspecified (the host form: the later ones); exactly `capacity` entries are live
+ * afterwards. A full table is left as it is; in the batch that fills it, a key that had taken its
+ * slot when the last place went leaves that slot a tombstone (the host form: none). Two launches on
+ * `stream`, no lane ever waits for another. d_keys is 16-byte aligned, d_result 4-byte. */
+NEB_API int neb_conntrack_add_batch(neb_engine* e, neb_conntrack* t, const neb_fw_packet* d_keys, const uint8_t* d_incoming,
+                                    uint32_t n, uint64_t now_ns, neb_ct_result* d_result, void* stream);
+NEB_API int neb_conntrack_add_batch_host(neb_conntrack* t, const neb_fw_packet* keys, const uint8_t* incoming, uint32_t n,
+                                         uint64_t now_ns, neb_ct_result* result);
+/* evict per key i (force: the stale entry's delete of firewall.go:545): absent -> -1; Expires >
+ * now_ns and force == 0 -> the remaining ns (> 0), the entry stays and the caller re-adds the key to
+ * its wheel; otherwise the entry is removed (its slot becomes a tombstone) and the result is 0. Every
+ * copy of a duplicated key reports what it found: 0 where the entry was still there, -1 behind the
+ * copy that removed it (the host form: the first copy 0, the others -1). d_keys is 16-byte aligned,
+ * d_remaining 8-byte. */
+NEB_API int neb_conntrack_evict_batch(neb_engine* e, neb_conntrack* t, const neb_fw_packet* d_keys, uint32_t n,
+                                      uint64_t now_ns, int force, int64_t* d_remaining, void* stream);
+NEB_API int neb_conntrack_evict_batch_host(neb_conntrack* t, const neb_fw_packet* keys, uint32_t n, uint64_t now_ns,
+                                           int force, int64_t* remaining);
+/* Rehashes every live entry into a cleared image (value fields kept) and switches over: tombstones
+ * drop to 0. Blocks until switched; no other call on t meanwhile. Recommended when live +
+ * tombstones > 3/4 of the slots. stream is ignored by a host-only table. */
+NEB_API int neb_conntrack_compact(neb_conntrack* t, void* stream);
+/* out = {live, tombstones, slots}; waits for the table's enqueued work. EmitStats'
+ * firewall.conntrack.count is out[0]. */
+NEB_API int neb_conntrack_count(neb_conntrack* t, uint64_t out[3]);
+/* For tests: the home slot of a key; and the image, nslots x 64 bytes {state, key[5], expires, meta}
+ * (conntrack_core.hpp), after the table's enqueued work. nslots must be the table's slot count. */
+NEB_API int neb_conntrack_home(const neb_conntrack* t, const neb_fw_packet* key, uint32_t* slot);
+NEB_API int neb_conntrack_dump(neb_conntrack* t, void* slots_out, uint32_t nslots);
 /* ---- submission queue: many threads' small flushes -> device-sized batches -------------------- */
 /* Nebula seals <= 128 packets per TX flush (overlay/batch/tx_batch.go:5, flushSendBatch
  * interface.go:465-487) and opens <= listen.batch = 64 per RX flush (main.go:181, listenOut

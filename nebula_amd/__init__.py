@@ -10,6 +10,7 @@ from ._lib import (ALG_AESGCM, ALG_CHACHAPOLY, DESC_DTYPE, KEYS_MIXED, OVERHEAD,
 from .noiseutil import (CipherAESGCM, CipherChaChaPoly, CipherState, CipherStateAESGCM, CipherStateChaChaPoly,
                         Engine, ErrMessageCounterExhausted, ErrNoCipher, ErrOpen, NewCipherState,
                         RejectAfterMessages, RejectHeadroom, Slice)
+from .firewall import Conntrack
 from .hostmap import IndexTable, PeerTable, TxTable
 from .outside import MultiCoalescer, coalesce_batch_device, coalesce_batch_host, inner_device, inner_host, receive
 from .relay import (relay_forward_batch, relay_forward_batch_device, rx_open_via_batch, rx_open_via_batch_device,
@@ -22,5 +23,5 @@ __all__ = [
     "NewCipherState", "RejectAfterMessages", "RejectHeadroom", "Slice", "_lib",
     "relay_forward_batch", "relay_forward_batch_device", "rx_open_via_batch", "rx_open_via_batch_device",
     "rx_via_unwrap", "IndexTable", "TxTable", "PeerTable", "inner_host", "inner_device",
-    "MultiCoalescer", "coalesce_batch_host", "coalesce_batch_device", "receive",
+    "MultiCoalescer", "coalesce_batch_host", "coalesce_batch_device", "receive", "Conntrack",
 ]

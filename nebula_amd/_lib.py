@@ -46,6 +46,7 @@ STATUS_RX_PEER_REJECTED = 14  # neb_rx_inner_batch: ErrPeerRejected
 STATUS_RX_BAD_LOCAL = 15  # neb_rx_inner_batch: ErrInvalidLocalIP
 STATUS_UNROUTABLE = 16  # neb_tx_send_plan: the socket cannot address the destination
 STATUS_NOT_SENT = 17  # neb_tx_send_plan: wire_status != OK, never committed to the SendBatch
+STATUS_FW_HELD = 18  # neb_conntrack_lookup_batch: held for the caller's rules (not an established flow)
 
 OVERHEAD = 16
 HEADER_LEN = 16
@@ -158,6 +159,18 @@ RX_RELAY_USED_DTYPE = np.dtype([("index", "<u4"), ("packets", "<u4")])
 RX_WORK_DTYPE = np.dtype([("packet", "<u4"), ("kind", "<u4")])
 assert RX_RUN_DTYPE.itemsize == 40 and RX_RELAY_USED_DTYPE.itemsize == 8 and RX_WORK_DTYPE.itemsize == 8
 
+# neb_conntrack_* (include/nebula_aead.h): firewall.Conntrack.Conns for TX and RX batches
+CT_NONE, CT_HIT, CT_MISS, CT_STALE, CT_INCOMING = 0, 1, 2, 3, 0x80
+CT_NEW, CT_EXISTING, CT_DUP, CT_FULL = 1, 2, 3, 4
+CT_NO_SLOT = 0xFFFFFFFF
+CT_MAX_CAPACITY = 1 << 22
+CT_WORK_DTYPE = np.dtype([("packet", "<u4"), ("verdict", "<u4"), ("fw", FW_PACKET_DTYPE), ("reserved", "u1", (8,))])
+CT_RESULT_DTYPE = np.dtype([("code", "<u4"), ("slot", "<u4")])
+# one slot of the image (csrc/conntrack_core.hpp), as neb_conntrack_dump gives it
+CT_SLOT_DTYPE = np.dtype([("state", "<u8"), ("key", "<u8", (5,)), ("expires", "<u8"), ("meta", "<u8")])
+CT_STATE_EMPTY, CT_STATE_TOMB, CT_STATE_KIND, CT_STATE_CLAIMED, CT_STATE_SETTLED = 0, 1, 3 << 62, 2 << 62, 3 << 62
+assert CT_WORK_DTYPE.itemsize == 64 and CT_RESULT_DTYPE.itemsize == 8 and CT_SLOT_DTYPE.itemsize == 64
+
 # Every symbol include/nebula_aead.h declares, with (restype, argtypes).
 _vp, _u8p, _sz, _u32, _u64, _i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
 SIGNATURES = {
@@ -258,6 +271,19 @@ SIGNATURES = {
     "neb_peer_table_probe": (_i, [_vp, _vp, C.POINTER(_u32)]),
     "neb_rx_inner_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "neb_rx_inner_batch_host": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp, _vp, _vp]),
+    "neb_conntrack_create": (_i, [_vp, _u32, _u64, _u64, _u64, _u64, _u32, C.POINTER(_vp)]),
+    "neb_conntrack_destroy": (_i, [_vp]),
+    "neb_conntrack_set_rules_version": (_i, [_vp, C.c_uint16]),
+    "neb_conntrack_lookup_batch": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "neb_conntrack_lookup_batch_host": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "neb_conntrack_add_batch": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp]),
+    "neb_conntrack_add_batch_host": (_i, [_vp, _vp, _vp, _u32, _u64, _vp]),
+    "neb_conntrack_evict_batch": (_i, [_vp, _vp, _vp, _u32, _u64, _i, _vp, _vp]),
+    "neb_conntrack_evict_batch_host": (_i, [_vp, _vp, _u32, _u64, _i, _vp]),
+    "neb_conntrack_compact": (_i, [_vp, _vp]),
+    "neb_conntrack_count": (_i, [_vp, C.POINTER(_u64)]),
+    "neb_conntrack_home": (_i, [_vp, _vp, C.POINTER(_u32)]),
+    "neb_conntrack_dump": (_i, [_vp, _vp, _u32]),
     "neb_seal_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_open_batch_host_multi": (_i, [_vp, _u32, _i, _vp, _u32, _vp, _sz, _vp, _u32]),
     "neb_seal_batch_sharded": (_i, [_i, _vp, _u32, _u32]),
